@@ -10,8 +10,16 @@ RCCL all-reduce inside the step ("weak" scaling); the all-reduce runs on its own
 stream, overlapped with the next step's scan (double-buffered aggregates). Data are synthetic
 (SURVEY.md §8(c) generator), generated on the device.
 
-  python bench.py [--gpus N --steps K --warmup W] [--rows R] [--no-cpu] [--no-extra]
+  python bench.py [--gpus N --steps K --warmup W] [--rows R] [--dump-outputs DIR]
+  python bench.py --full [...] [--no-cpu] [--no-extra]
   python bench.py --inproc [--gpus N]   libmq's own row-shard path, one process (inproc_main)
+
+A plain run sets up, warms up, times the K steps and prints the result line; --full
+adds every secondary measurement (the streaming-read probe, the extra legs, the
+cpu_baseline), each of which takes runs of its own. --dump-outputs DIR writes what the
+last timed step returned to its caller as DIR/select_sum.npy (float64: count, sum,
+min, max of mq_agg); the inputs are generated from fixed seeds, so two builds can be
+compared output for output.
 
 Rank 0 prints ONE JSON line. Roofline: algorithmic bytes 4N per scan launch ÷ the
 scan kernel's mean duration from HIP events on the launch stream. cpu_baseline:
@@ -361,8 +369,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rows", type=int, default=1_000_000_000)
     ap.add_argument("--sel", type=float, default=0.01)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the positions/config-3 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: streaming-read probe, extra legs, cpu_baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the positions/config-3 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     ap.add_argument("--join", action="store_true",
                     help="N > 1: also time config 5 key-partitioned over the ranks (dist.partitioned_join)")
     args = ap.parse_args()
@@ -475,12 +487,15 @@ def main() -> None:
         want_s = sum(rows[s]["sum"] for s in range(42, 42 + world))
         parity = (res["count"], res["sum"]) == (want_k, want_s)
 
-    achievable = achievable_read_peak(lib, mq, torch, stream, col, ws) if world == 1 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+
+    achievable = achievable_read_peak(lib, mq, torch, stream, col, ws) if world == 1 and args.full else None
 
     extra = {}
     if world > 1 and args.join:  # every rank takes part (all_to_all exchanges)
         extra["config5_partitioned_join"] = dist_join_leg(lib, mq, mqd, torch, dist, dev, rank, world, gold)
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         extra = extra_legs(lib, mq, torch, dev, stream, col, ws, ws_bytes, n, lo, hi, gold,
                            cpu=not args.no_cpu)
 
@@ -519,7 +534,7 @@ def main() -> None:
             "parity": {"ok": parity, "count": res["count"], "sum": res["sum"]},
             "extra": extra,
         }
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(n)
         bad = parity_failures(out)
         out["parity_failures"] = bad
@@ -532,6 +547,16 @@ def main() -> None:
     if parity is False or (rank == 0 and bad):
         print(f"bench.py: parity FAILED: {'headline' if parity is False else ''} {bad}", file=sys.stderr)
         sys.exit(1)
+
+
+def dump_outputs(path: str, res: dict) -> None:
+    """--dump-outputs: the last timed step's mq_agg as the caller receives it (over
+    all ranks for N > 1), as float64 [count, sum, min, max] in DIR/select_sum.npy.
+    One GPU's 1e9-row sum (about 2.6e15) is below 2^53, so float64 holds it exactly."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "select_sum.npy"),
+            np.array([res["count"], res["sum"], res["min"], res["max"]], dtype=np.float64))
 
 
 def dist_join_leg(lib, mq, mqd, torch, dist, dev, rank, world, gold, logn: int = 28, reps: int = 3) -> dict:

@@ -93,18 +93,26 @@ class Server:
             os.unlink(sock)
         self.proc = subprocess.Popen([self.binary], cwd=self.workdir, stdout=self.log,
                                      stderr=subprocess.STDOUT, start_new_session=True)
-        deadline = time.time() + 60
-        while time.time() < deadline:
-            if self.proc.poll() is not None:
-                raise RuntimeError(f"{self.binary} exited early ({self.proc.returncode})")
-            if os.path.exists(sock):
-                try:
-                    with socket.socket(socket.AF_UNIX) as s:
-                        s.connect(sock)
-                    return
-                except OSError:
-                    pass
-            time.sleep(0.05)
+        # The server binds the relative SOCK in its workdir; sockaddr_un holds 108
+        # bytes, which workdir + SOCK may exceed (a deep pytest tmp_path), so connect
+        # through the workdir's descriptor: a short path to the same socket.
+        dirfd = os.open(self.workdir, os.O_RDONLY | os.O_DIRECTORY)
+        try:
+            short = f"/proc/self/fd/{dirfd}/{SOCK}"
+            deadline = time.time() + 60
+            while time.time() < deadline:
+                if self.proc.poll() is not None:
+                    raise RuntimeError(f"{self.binary} exited early ({self.proc.returncode})")
+                if os.path.exists(sock):
+                    try:
+                        with socket.socket(socket.AF_UNIX) as s:
+                            s.connect(short)
+                        return
+                    except OSError:
+                        pass
+                time.sleep(0.05)
+        finally:
+            os.close(dirfd)
         raise RuntimeError(f"{self.binary} did not open {SOCK}")
 
     def stop(self):
