@@ -1208,6 +1208,77 @@ static size_t hashset_gpu_min(void) {
     return e ? (size_t)strtoull(e, NULL, 10) : (size_t)32768;
 }
 
+/* Keys from which a bulk insert builds the table on the GPU: MQ_HASHSET_GPU_MIN as
+ * for the listing, with a default of its own (the measured crossover against the
+ * host loop with the table's upload and download counted). */
+#define HASHSET_INSERT_GPU_MIN_KEYS 32768
+static size_t hashset_insert_gpu_min(void) {
+    const char* e = getenv("MQ_HASHSET_GPU_MIN");
+    return e ? (size_t)strtoull(e, NULL, 10) : (size_t)HASHSET_INSERT_GPU_MIN_KEYS;
+}
+
+static int hashset_bulk_args(const char* who, const hashset* set, const void* keys, size_t n) {
+    if (set && set->size > 0 && set->keys && (keys || n == 0)) return 0;
+    fprintf(stderr, "libmq: %s: bad argument\n", who);
+    return MQ_EINVAL;
+}
+
+/* 1 when n keys go to the device: enough of them, ranks that fit 32 bits, a device. */
+static int hashset_bulk_on_gpu(size_t n) {
+    return n >= hashset_insert_gpu_min() && n > 0 && (uint64_t)n < 0xFFFFFFFFull && op_begin(NULL) == 0;
+}
+
+/* The table to HBM, mq_hashset_insert of the n keys at d_keys (resident) or h_keys
+ * (uploaded behind the table), the table back. set->keys is written only by the final
+ * copy, which starts after the stream has drained without an error. */
+static int hashset_insert_device(hashset* set, const int32_t* d_keys, const int* h_keys, size_t n) {
+    const size_t size = (size_t)set->size;
+    const size_t tab_bytes = (size * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t key_bytes = d_keys ? 0 : (n * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t ws_bytes = mq_hashset_insert_workspace_bytes(size, n);
+    void* d_buf = NULL;
+    int rc = dev_alloc(&d_buf, tab_bytes + key_bytes + ws_bytes);
+    if (rc) return fail(NULL, "hashset insert allocation", rc);
+    int32_t* d_tab = (int32_t*)d_buf;
+    if (!d_keys) {
+        d_keys = (const int32_t*)((char*)d_buf + tab_bytes);
+        rc = h2d((void*)d_keys, h_keys, n * sizeof(int32_t));
+    }
+    if (!rc && !(rc = h2d(d_tab, set->keys, size * sizeof(int32_t))) &&
+        !(rc = mq_hashset_insert(d_tab, set->size, d_keys, n, NULL, (char*)d_buf + tab_bytes + key_bytes,
+                                 ws_bytes, g_stream)))
+        rc = d2h(set->keys, d_tab, size * sizeof(int32_t));
+    if (rc) mq_stream_sync(g_stream); /* nothing queued may still use the block */
+    mq_pool_free(d_buf);
+    return rc ? fail(NULL, "hashset insert on the GPU", rc) : 0;
+}
+
+int mq_hashset_insert_many(hashset* set, const int* keys, size_t n) {
+    int rc = hashset_bulk_args("mq_hashset_insert_many", set, keys, n);
+    if (rc) return rc;
+    if (hashset_bulk_on_gpu(n)) return hashset_insert_device(set, NULL, keys, n);
+    for (size_t i = 0; i < n; i++) insert_hashset(set, keys[i]);
+    return 0;
+}
+
+int mq_hashset_insert_result(hashset* set, const Result* keys) {
+    if (!keys || keys->data_type != INT) {
+        fprintf(stderr, "libmq: mq_hashset_insert_result: not an INT Result\n");
+        return MQ_EINVAL;
+    }
+    const size_t n = keys->num_tuples;
+    int rc = hashset_bulk_args("mq_hashset_insert_result", set, keys->payload, n);
+    if (rc) return rc;
+    if (hashset_bulk_on_gpu(n)) {
+        const int32_t* d_keys; /* the payload's HBM shadow when one is resident */
+        if (result_device(keys, &d_keys, NULL)) return MQ_EHIP;
+        return hashset_insert_device(set, d_keys, NULL, n);
+    }
+    const int* h = (const int*)keys->payload;
+    for (size_t i = 0; i < n; i++) insert_hashset(set, h[i]);
+    return 0;
+}
+
 Result* get_hashset_elements(hashset* set) {
     const size_t size = set && set->size > 0 ? (size_t)set->size : 0;
     if (size >= hashset_gpu_min() && ready(NULL) == 0) {

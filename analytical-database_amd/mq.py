@@ -143,6 +143,10 @@ _SIGS = {
     "mq_stream_read": (_int, [_vp, _u64, _vp, _sz, C.POINTER(C.c_uint64), _vp]),
     "mq_hashset_lookup": (_int, [_vp, _i32, _vp, _u64, _vp, _vp]),
     "mq_hashset_elements": (_int, [_vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "mq_hashset_insert_workspace_bytes": (_sz, [_u64, _u64]),
+    "mq_hashset_insert": (_int, [_vp, _i32, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "mq_hashset_insert_many": (_int, [_vp, _vp, _sz]),
+    "mq_hashset_insert_result": (_int, [_vp, _PR]),
     "mq_random_read": (_int, [_vp, _int, _u64, _vp, _vp]),
     "mq_select_fetch_agg": (_int, [_vp, _vp, _u64, _int, _i32, _int, _i32, _vp, _vp, _sz, _vp]),
     "mq_select_positions_at": (_int, [_vp, _vp, _u64, _i32, _int, _i32, _int, _i32, _vp, _vp, _vp, _sz,

@@ -162,6 +162,22 @@ int mq_hashset_lookup(const int32_t* d_table, int32_t size, const int32_t* d_pro
                       uint8_t* d_found, void* stream);
 int mq_hashset_elements(const int32_t* d_table, uint64_t size, int32_t* d_out, uint64_t* d_count,
                         void* d_ws, size_t ws_bytes, void* stream);
+/* mq_hashset_insert: the bulk form of insert_hashset (hashset.c:25-32). d_table holds
+ *   `size` slots, all zero or left by earlier inserts; afterwards it holds exactly the
+ *   slots that `for i in 0..n-1: insert_hashset(set, d_keys[i])` leaves: key 0 is never
+ *   stored, a repeated key keeps its first place, and a key that finds no free slot in
+ *   one lap is dropped (the reference loops forever). The layout does not depend on
+ *   how the blocks are scheduled: the build is a linear probe ordered by first
+ *   occurrence over a 64-bit working copy of the table. *d_stored
+ *   (device, may be NULL) receives the number of nonzero slots afterwards. d_ws:
+ *   mq_hashset_insert_workspace_bytes(size, n) bytes (8 per slot, and 8 per slot of a
+ *   scratch table of the first power of two >= 2n slots). Asynchronous on `stream`.
+ *   n == 0 leaves the table untouched. MQ_EINVAL for size <= 0, a NULL table, NULL keys
+ *   with n > 0, n >= 2^32 - 1 or a short workspace. Keys that share one home slot cost
+ *   O(n^2) probe steps, as in the reference. */
+size_t mq_hashset_insert_workspace_bytes(uint64_t size, uint64_t n);
+int mq_hashset_insert(int32_t* d_table, int32_t size, const int32_t* d_keys, uint64_t n,
+                      uint64_t* d_stored, void* d_ws, size_t ws_bytes, void* stream);
 
 /* Config-3 fused: aggregate of d_val[i] over rows i where d_sel[i] is in range. */
 int mq_select_fetch_agg(const int32_t* d_sel, const int32_t* d_val, uint64_t n, int has_low,

@@ -165,6 +165,17 @@ void free_hashset(hashset* set);                   /* hashset.c:19-22 */
 void insert_hashset(hashset* set, int key);        /* hashset.c:25-32 */
 bool lookup_hashset(hashset* set, int key);        /* hashset.c:35-45 */
 Result* get_hashset_elements(hashset* set);        /* hashset.c:48-65 */
+/* Bulk inserts (not in hashset.h): set->keys afterwards holds exactly what
+ * `for i in 0..n-1: insert_hashset(set, keys[i])` leaves. From MQ_HASHSET_GPU_MIN
+ * keys on (default 32768) and with a device the table is built in HBM
+ * (mq_hashset_insert, mq_device.h): table up, build, table down; below that, or
+ * without a device, it is that host loop. mq_hashset_insert_result takes the keys of
+ * an INT Result (a fetch_column's output, say) from its HBM shadow when one is
+ * resident, so they are not uploaded again. Both return 0 or a negative MQ_E* code
+ * (MQ_EINVAL for a NULL set, keys or a Result that is not INT); after a device failure
+ * set->keys is unchanged and mq_last_error() has the text. */
+int mq_hashset_insert_many(hashset* set, const int* keys, size_t n);
+int mq_hashset_insert_result(hashset* set, const Result* keys);
 
 /* ---- the load path (db_manager.h:254) ----
  * load_db (db_manager.c:240-322 with insert_row :164-199): same header check
