@@ -721,11 +721,9 @@ static IndexEntry* idx_put(ColumnIndex* ix, size_t n, void* d_values, void* d_po
     return &g_idx[g_nidx - 1];
 }
 
-/* query.c:165-198: sorted-index select, in value order. */
-Result* select_column_sorted_index(Column* column, int low, int high, Status* ret_status) {
-    if (op_begin(ret_status)) return NULL;
-    ColumnIndex* ix = column->index;
-    size_t n = column->row_count;
+/* The HBM copy of an index's arrays over n rows: the resident one while it is usable,
+ * else an upload. NULL after a failure (reported). */
+static IndexEntry* index_device(ColumnIndex* ix, size_t n, Status* ret_status) {
     IndexEntry* e = NULL;
     for (int i = 0; i < g_nidx; i++)
         if (g_idx[i].index == ix) e = &g_idx[i];
@@ -747,7 +745,15 @@ Result* select_column_sorted_index(Column* column, int low, int high, Status* re
         e = idx_put(ix, n, dv, dp, 0); /* the caller's arrays: single-use */
     }
     e->op = g_op;
-    if (ensure_ws(n, ret_status)) return NULL;
+    return e;
+}
+
+/* query.c:165-198: sorted-index select, in value order. */
+Result* select_column_sorted_index(Column* column, int low, int high, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    size_t n = column->row_count;
+    IndexEntry* e = index_device(column->index, n, ret_status);
+    if (!e || ensure_ws(n, ret_status)) return NULL;
     int rc = mq_index_select((const int32_t*)e->d_values, (const uint64_t*)e->d_positions, n, low, high,
                              (int32_t*)g_scratch, (uint64_t*)g_small, g_stream);
     if (rc) {
@@ -1598,6 +1604,205 @@ void build_index(Db* db) {
             if (c->has_index && index_one(t, c, &st)) return; /* build_btree is a no-op */
         }
     }
+}
+
+/* ------------------------------------------------------------------ */
+/* row deletes and updates (the generator's milestone 5; no reference  */
+/* counterpart: parse.c:876-960 has no branch for either command)      */
+/* ------------------------------------------------------------------ */
+
+static void dml_fail(Status* st, const char* what, const char* msg) {
+    fprintf(stderr, "libmq: %s: %s\n", what, msg);
+    st->code = ERROR;
+    st->error_message = (char*)msg;
+}
+
+/* Before a write operator works on a column: an attached copy is the caller's memory
+ * and is never written, a sharded copy is split again on next use (both as
+ * mq_column_invalidate does); an owned copy stays. */
+static void dml_detach(Column* c) {
+    ColEntry* e = col_find(c);
+    if (e && !e->owned) col_drop(e);
+    shard_forget_column(c);
+}
+
+static int index_built(const Column* c) {
+    return c->has_index && c->index && c->index->values && c->index->positions;
+}
+
+/* relational_delete(db1.tbl5,d1), milestone5.py:186-202: the listed rows leave every
+ * column of the table, the survivors keep their order. All device work is done before
+ * anything on the host changes. */
+void relational_delete(Table* table, Result* positions, Status* ret_status) {
+    if (op_begin(ret_status)) return;
+    ret_status->code = OK;
+    if (!table || !positions || positions->data_type != INT || (positions->num_tuples && !positions->payload)) {
+        dml_fail(ret_status, "relational_delete", "the positions must be an INT Result");
+        return;
+    }
+    const size_t n = table->row_count, k = positions->num_tuples;
+    const int ncols = (int)table->col_count;
+    if (table->col_count > 1024 || n >= ((size_t)1 << 31)) {
+        dml_fail(ret_status, "relational_delete", "more than 1024 columns or 2^31 rows");
+        return;
+    }
+    for (int j = 0; j < ncols; j++)
+        if (table->columns[j].row_count != n) {
+            dml_fail(ret_status, "relational_delete", "a column's row_count differs from the table's");
+            return;
+        }
+    if (k == 0) return;
+    const int32_t* dcol[1024];
+    void* dnew[1024] = {NULL};
+    void *ws = NULL, *dh = NULL;
+    void **div = NULL, **dip = NULL; /* the maintained indexes' new arrays, per column */
+    const int32_t* dpos;
+    uint64_t deleted = 0, bad = 0;
+    int rc = 0;
+    if (result_device(positions, &dpos, ret_status)) return;
+    const size_t wsb = mq_delete_workspace_bytes(n);
+    if ((rc = dev_alloc(&ws, wsb))) {
+        fail(ret_status, "relational_delete workspace", rc);
+        return;
+    }
+    rc = mq_delete_plan(dpos, k, n, &deleted, &bad, ws, wsb, g_stream);
+    if (rc) {
+        if (bad) {
+            dml_fail(ret_status, "relational_delete", "a row id lies outside the table");
+            rc = 0;
+        }
+        goto out;
+    }
+    if (deleted == 0) goto out;
+    const size_t left = n - (size_t)deleted;
+    if (!(div = calloc((size_t)ncols, sizeof *div)) || !(dip = calloc((size_t)ncols, sizeof *dip))) {
+        rc = MQ_ENOMEM;
+        goto out;
+    }
+    for (int j = 0; j < ncols; j++) {
+        Column* c = table->columns + j;
+        dml_detach(c);
+        Status s = {OK, NULL};
+        if ((rc = column_device(c, &dcol[j], &s)) || (rc = dev_alloc(&dnew[j], (left ? left : 1) * 4))) goto out;
+    }
+    if ((rc = mq_delete_columns(ws, dcol, ncols, (int32_t* const*)dnew, g_stream))) goto out;
+    for (int j = 0; j < ncols; j++) {
+        Column* c = table->columns + j;
+        if (!index_built(c)) continue;
+        Status s = {OK, NULL};
+        IndexEntry* e = index_device(c->index, n, &s);
+        if (!e) {
+            rc = MQ_EHIP;
+            goto out;
+        }
+        if ((rc = dev_alloc(&div[j], (left ? left : 1) * 4)) || (rc = dev_alloc(&dip[j], (left ? left : 1) * 8)) ||
+            (rc = mq_delete_index(ws, (const int32_t*)e->d_values, (const uint64_t*)e->d_positions, (int32_t*)div[j],
+                                  (uint64_t*)dip[j], g_stream)))
+            goto out;
+    }
+    /* commit: the host rows (guard range forgotten first, as index_one does for reordered
+     * columns), the counts, and the new device arrays as the resident copies */
+    for (int j = 0; j < ncols; j++) {
+        Column* c = table->columns + j;
+        mq_guard_forget_range((uintptr_t)c->data, n * 4);
+        if (left && (rc = d2h(c->data, dnew[j], left * 4))) goto out;
+        c->row_count = left;
+        col_put(c, dnew[j]);
+        void* d_rows = dnew[j];
+        dnew[j] = NULL;
+        if (!div[j]) continue;
+        ColumnIndex* ix = c->index;
+        mq_guard_forget_range((uintptr_t)ix->values, n * 4);
+        mq_guard_forget_range((uintptr_t)ix->positions, n * 8);
+        if (left && ((rc = d2h(ix->values, div[j], left * 4)) || (rc = d2h(ix->positions, dip[j], left * 8)))) goto out;
+        idx_put(ix, left, div[j], dip[j], 1); /* replaces the entry over n rows */
+        div[j] = dip[j] = NULL;
+        MqHistogram* h = (MqHistogram*)c->histogram;
+        if (!c->clustered && h && h->bin_size != 0) { /* bin_size and values[] stay; the counts follow the rows */
+            uint64_t counts[MQ_BIN_NUM + 1];
+            if ((!dh && (rc = mq_malloc(&dh, sizeof counts))) ||
+                (rc = mq_histogram((const int32_t*)d_rows, left, c->min, h->bin_size, dh, g_stream)) ||
+                (rc = d2h(counts, dh, sizeof counts)))
+                goto out;
+            for (int b = 0; b < MQ_BIN_NUM; b++) h->counts[b] = counts[b];
+        }
+    }
+    table->row_count = left;
+out:
+    mq_stream_sync(g_stream);
+    for (int j = 0; j < ncols; j++) {
+        mq_pool_free(dnew[j]);
+        if (div) mq_pool_free(div[j]);
+        if (dip) mq_pool_free(dip[j]);
+    }
+    free(div);
+    free(dip);
+    mq_pool_free(ws);
+    mq_pool_free(dh);
+    if (rc) fail(ret_status, "relational_delete", rc);
+}
+
+/* relational_update(db1.tbl5.col1,u1,-10), milestone5.py:127-142: one value to the
+ * listed rows of one column, on the host rows and on the resident copy alike. */
+void relational_update(Column* column, Result* positions, int value, Status* ret_status) {
+    if (op_begin(ret_status)) return;
+    ret_status->code = OK;
+    if (!column || !positions || positions->data_type != INT || (positions->num_tuples && !positions->payload)) {
+        dml_fail(ret_status, "relational_update", "the positions must be an INT Result");
+        return;
+    }
+    if (column->clustered) {
+        dml_fail(ret_status, "relational_update",
+                 "the column carries a clustered index: its rows are not in the table's row order");
+        return;
+    }
+    const size_t n = column->row_count, k = positions->num_tuples;
+    const int32_t* ids = (const int32_t*)positions->payload;
+    if (n >= ((size_t)1 << 31)) {
+        dml_fail(ret_status, "relational_update", "2^31 rows or more");
+        return;
+    }
+    for (size_t i = 0; i < k; i++)
+        if ((uint32_t)ids[i] >= n) {
+            dml_fail(ret_status, "relational_update", "a row id lies outside the column");
+            return;
+        }
+    if (k == 0) return;
+    dml_detach(column);
+    const int32_t *dcol, *dpos;
+    if (column_device(column, &dcol, ret_status) || result_device(positions, &dpos, ret_status)) return;
+    int rc = mq_update_rows((int32_t*)dcol, n, dpos, k, value, NULL, g_stream);
+    if (rc) {
+        fail(ret_status, "relational_update", rc);
+        mq_column_invalidate(column);
+        return;
+    }
+    mq_guard_forget_range((uintptr_t)column->data, n * 4); /* libmq writes the rows in place */
+    for (size_t i = 0; i < k; i++) column->data[ids[i]] = value;
+    column->max = column->max > value ? column->max : value; /* insert_row, db_manager.c:193-194 */
+    column->min = column->min < value ? column->min : value;
+    /* the copy now mirrors the new rows: register it again, which guards them afresh */
+    ColEntry* e = col_find(column);
+    void* dev = e->dev;
+    e->dev = NULL;
+    col_put(column, dev);
+    if (!index_built(column)) return;
+    /* an unclustered index on the column: built again by build_index's own routine */
+    ColumnIndex* ix = column->index;
+    for (int i = 0; i < g_nidx; i++)
+        if (g_idx[i].index == ix) {
+            idx_drop(&g_idx[i]);
+            break;
+        }
+    mq_guard_forget_range((uintptr_t)ix->values, n * 4);
+    mq_guard_forget_range((uintptr_t)ix->positions, n * 8);
+    free(ix->values);
+    free(ix->positions);
+    free(ix);
+    free(column->histogram);
+    column->index = NULL;
+    column->histogram = NULL;
+    if (index_one(NULL, column, ret_status)) ret_status->code = ERROR;
 }
 
 /* ------------------------------------------------------------------ */

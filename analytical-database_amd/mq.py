@@ -162,6 +162,11 @@ _SIGS = {
     "mq_index_build_ref": (_int, [_vp, _u64, _vp, _vp, _u64, C.POINTER(_int), _vp]),
     "mq_gather_u64": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_histogram": (_int, [_vp, _u64, _i32, _i32, _vp, _vp]),
+    "mq_delete_workspace_bytes": (_sz, [_u64]),
+    "mq_delete_plan": (_int, [_vp, _u64, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp, _sz, _vp]),
+    "mq_delete_columns": (_int, [_vp, _vp, _int, _vp, _vp]),
+    "mq_delete_index": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mq_update_rows": (_int, [_vp, _u64, _vp, _u64, _i32, _vp, _vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -209,6 +214,9 @@ _SIGS = {
     # load path (db_manager.h:254)
     "load_db": (None, [C.POINTER(Db), C.c_char_p, _PS]),
     "build_index": (None, [C.POINTER(Db)]),
+    # row deletes and updates (the generator's milestone 5)
+    "relational_delete": (None, [C.POINTER(Table), _PR, _PS]),
+    "relational_update": (None, [C.POINTER(Column), _PR, _int, _PS]),
     # residency
     "mq_column_attach": (_int, [C.POINTER(Column), _vp]),
     "mq_column_upload": (_int, [C.POINTER(Column)]),

@@ -248,6 +248,44 @@ int mq_gather_u64(const int32_t* d_col, const uint64_t* d_positions, uint64_t n,
 int mq_histogram(const int32_t* d_col, uint64_t n, int32_t col_min, int32_t bin_size,
                  uint64_t* d_counts, void* stream);
 
+/* ---- row deletes and updates by a position list ----
+ * The write path behind relational_delete / relational_update (mq_query.h). The
+ * reference has no such operator (its parser lacks both commands); the semantics are
+ * its workload generator's (milestone5.py:127-142, 186-202): a delete drops the listed
+ * rows from every column of a table and the survivors keep their order, an update
+ * assigns one value to the listed rows of one column. A delete is a plan and two apply
+ * steps on one workspace of mq_delete_workspace_bytes(n) bytes (16-byte aligned):
+ * plan:    d_pos holds k int32 row ids of a table of n < 2^31 rows, in any order,
+ *          repeats allowed. Builds one bit per row and the count of deleted rows before
+ *          each 64-bit word of them. Synchronises; *h_deleted = distinct rows marked,
+ *          *h_bad = ids outside [0, n). With *h_bad != 0 it returns MQ_EINVAL and leaves
+ *          no plan. k == 0 is a valid plan that deletes nothing.
+ * columns: d_out[j] (capacity n - deleted) receives the surviving rows of d_cols[j] in
+ *          ascending row order, for ncols <= 1024 columns; d_cols / d_out are host arrays
+ *          of device pointers, d_out[j] != d_cols[j]. Per column 4n bytes read,
+ *          4(n - deleted) written and 3n/16 of bitmap and word counts.
+ * index:   a sorted index over the same n rows (d_values ascending, d_positions size_t
+ *          row ids, a permutation of the rows: the identity for a clustered index):
+ *          the entries whose row survives, in their order, each position p renumbered
+ *          to p - (deleted rows before p). Either output may be NULL only when nothing
+ *          survives. Its temporaries live in the workspace.
+ * Both apply steps run on the plan the calling thread made last, on that workspace and
+ * device, are asynchronous on `stream`, and may be repeated (other columns, other
+ * indexes) while the workspace is untouched.
+ * mq_update_rows: d_col[d_pos[i]] = value for every id in [0, n); ids outside are
+ *          skipped and *d_bad (device, may be NULL) receives their number. Repeated ids
+ *          are harmless. Asynchronous on `stream`.
+ * MQ_EINVAL: NULL pointers, n >= 2^31, a short or misaligned workspace, no plan. */
+size_t mq_delete_workspace_bytes(uint64_t n);
+int mq_delete_plan(const int32_t* d_pos, uint64_t k, uint64_t n, uint64_t* h_deleted,
+                   uint64_t* h_bad, void* d_ws, size_t ws_bytes, void* stream);
+int mq_delete_columns(const void* d_ws, const int32_t* const* d_cols, int ncols,
+                      int32_t* const* d_out, void* stream);
+int mq_delete_index(void* d_ws, const int32_t* d_values, const uint64_t* d_positions,
+                    int32_t* d_values_out, uint64_t* d_positions_out, void* stream);
+int mq_update_rows(int32_t* d_col, uint64_t n, const int32_t* d_pos, uint64_t k, int32_t value,
+                   uint64_t* d_bad, void* stream);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

@@ -200,6 +200,38 @@ void load_db(Db* db, const char* path, Status* ret_status);
  * instead of index.o's. */
 void build_index(Db* db);
 
+/* ---- row deletes and updates (the workload generator's milestone 5) ----
+ * The DSL of the reference's tests 38-43: relational_delete(db1.tbl5,d1) and
+ * relational_update(db1.tbl5.col1,u1,-10). The reference declares no such functions and
+ * its parser has no branch for the commands (parse.c:876-960; its server crashes on
+ * those tests), so nothing clashes at link time and the semantics are the
+ * generator's pandas statements (milestone5.py:127-142, 186-202). Argument order as in
+ * the DSL, Status as insert_row. `positions` is an INT Result of row ids, in any order,
+ * repeats allowed (a select_column's output); its HBM shadow is used when resident.
+ * Both work on the columns' resident copies and leave them resident,
+ * so the next operator uploads nothing. Without a device, or with a row id outside the
+ * table, they set ERROR and change nothing. A copy attached with mq_column_attach is
+ * detached first (the caller's buffer is never written); a column held as row shards
+ * drops its shards and is split again on next use.
+ * relational_delete: the listed rows leave every column of the table (each column's
+ *   row_count must equal table->row_count), the survivors keep their order.
+ *   column->data holds the surviving rows, table->row_count and every column's
+ *   row_count drop by the number of distinct ids; table_length and the host rows
+ *   beyond the new count are left alone, and so are min / max (the reference only ever
+ *   widens them, db_manager.c:193-194; they stay valid bounds). Every built index of
+ *   the table keeps its entries of surviving rows, in their order, renumbered, in the
+ *   same host arrays (the first row_count entries); an unclustered column's histogram
+ *   counts are recomputed (bin_size and values[] stay). An empty Result changes nothing.
+ * relational_update: column->data[id] = value for every listed id; max / min widen as
+ *   insert_row's do; an unclustered index on the column is freed and built again as
+ *   build_index builds it. A column with `clustered` set answers ERROR: the reference's
+ *   clustered build sorts the index and reorders every OTHER column but leaves this
+ *   column's own rows as loaded (index.c:128-133; SURVEY.md §4, FAIL 25), so no row of
+ *   it corresponds to a row of the table. The other columns of such a table update
+ *   normally. */
+void relational_delete(Table* table, Result* positions, Status* ret_status);
+void relational_update(Column* column, Result* positions, int value, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
