@@ -28,7 +28,7 @@ uint32_t stream_grid(const DevState* s, uint64_t work_items);
 // kernel whose registers allow fewer than 8 blocks per CU would otherwise run a
 // second, partial round of blocks).
 uint32_t resident_grid(const DevState* s, uint64_t work_items, const void* fn);
-// Device exclusive scan u32[n] -> u64[n] (mq_join.hip); scratch holds
+// Device exclusive scan u32[n] -> u64[n] (mq_scan.hip); scratch holds
 // scan_u32_scratch_elems(n) u64.
 uint64_t scan_u32_scratch_elems(uint64_t n);
 int scan_u32_exclusive(const uint32_t* in, unsigned long long* out, uint64_t n,
@@ -41,7 +41,7 @@ int scan_u64_exclusive(const unsigned long long* in, unsigned long long* out, ui
                        unsigned long long* scratch, hipStream_t st);
 
 // Stable LSD radix sort (4 x 8-bit digits) of (int32 key, u32 value) pairs by key
-// (mq_join.hip). vals == nullptr sorts (key, row id). *keys_out receives the keys
+// (mq_rsort.hip). vals == nullptr sorts (key, row id). *keys_out receives the keys
 // as (uint32)key ^ 0x80000000 (ascending as unsigned), *vals_out the values; both
 // are pool_alloc'd (the caller pool_frees them). Synchronises the stream.
 int radix_sort_pairs(const int* keys, const int* vals, uint64_t n, uint32_t** keys_out,
@@ -50,7 +50,7 @@ int radix_sort_pairs(const int* keys, const int* vals, uint64_t n, uint32_t** ke
 // (int32, may be NULL) and positions (size_t rows, may be NULL), equal values in
 // ascending row order. Synchronises. Picks the form by the key range (mq_isort.hip).
 int radix_sort_index(const int* col, uint64_t n, int32_t* values, uint64_t* positions, hipStream_t st);
-// Its LSD form (mq_join.hip): npass 8-bit digits of (col ^ 2^31) - kmin.
+// Its LSD form (mq_rsort.hip): npass 8-bit digits of (col ^ 2^31) - kmin.
 int radix_sort_lsd_index(const int* col, uint64_t n, uint32_t kmin, int npass, int32_t* values, uint64_t* positions,
                          hipStream_t st);
 

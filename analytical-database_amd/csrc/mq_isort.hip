@@ -4,7 +4,7 @@
 //
 // The key range picks the form. One read of the column (mq_reduce) gives min and max;
 // keys are k = (value ^ 2^31) - min, b = bit length of max - min.
-// * b <= 24, or fewer than 2^22 rows: the LSD radix sort of mq_join.hip with
+// * b <= 24, or fewer than 2^22 rows: the LSD radix sort of mq_rsort.hip with
 //   ceil(b / 8) passes instead of 4 (every pass reads and writes all n words).
 // * otherwise MSD levels, then one LDS pass per range:
 //   - a level splits each of its ranges by the next w <= 8 key bits: per tile of 8192

@@ -1039,7 +1039,7 @@ __global__ __launch_bounds__(kTPB) void k_iota(int* __restrict__ out, uint64_t n
 
 }  // namespace
 
-// host runtime shared with mq_join.hip (mq_common.h)
+// host runtime shared with the other HIP sources (mq_common.h)
 namespace mqi {
 thread_local char g_err[512] = "";
 

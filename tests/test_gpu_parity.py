@@ -801,7 +801,7 @@ def test_hash_join_partitioned_probe(lib, refcpu, monkeypatch, mode, case):
 
 
 def _inv_fmix32(h):
-    """Inverse of libmq's table hash (the murmur3 finaliser, mq_join.hip hash32), so a
+    """Inverse of libmq's table hash (the murmur3 finaliser, mq_join_impl.h hash32), so a
     test can pick the home slot of every key."""
     M = np.uint64(0xFFFFFFFF)
     x = h.astype(np.uint64)
