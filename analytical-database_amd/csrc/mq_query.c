@@ -1505,6 +1505,32 @@ static uint64_t index_exact_max(void) {
     return e ? (uint64_t)strtoull(e, NULL, 10) : ((uint64_t)1 << 27);
 }
 
+/* build_histogram (index.c:63-84) of column c over its n rows dcol: bin_size from the
+ * column's min / max, the bin starts, and the counts from mq_histogram. *dh: device
+ * scratch for the counts, allocated here when NULL (the caller frees it). */
+static int histogram_fill(const char* who, const Column* c, MqHistogram* h, const int32_t* dcol, size_t n, void** dh) {
+    h->bin_size = (c->max - c->min) / (MQ_BIN_NUM - 1);
+    memset(h->values, 0, sizeof h->values);
+    memset(h->counts, 0, sizeof h->counts);
+    size_t bin_start = 0;
+    for (int b = 0; b < MQ_BIN_NUM; b++) {
+        h->values[b] = (int)bin_start;
+        bin_start += (size_t)(long)h->bin_size;
+    }
+    if (h->bin_size == 0) {
+        fprintf(stderr, "libmq: %s: column %s spans < %d values; histogram counts left 0 "
+                        "(the reference divides by zero here)\n", who, c->name, MQ_BIN_NUM - 1);
+        return 0;
+    }
+    uint64_t counts[MQ_BIN_NUM + 1];
+    int rc;
+    if ((!*dh && (rc = mq_malloc(dh, sizeof counts))) ||
+        (rc = mq_histogram(dcol, n, c->min, h->bin_size, *dh, g_stream)) || (rc = d2h(counts, *dh, sizeof counts)))
+        return rc;
+    for (int b = 0; b < MQ_BIN_NUM; b++) h->counts[b] = counts[b];
+    return 0;
+}
+
 /* One indexed column (index.c:119-143 + :63-84). Returns 0 or an MQ_E code. */
 static int index_one(Table* t, Column* c, Status* st) {
     const size_t n = c->row_count;
@@ -1555,26 +1581,9 @@ static int index_one(Table* t, Column* c, Status* st) {
             rc = MQ_ENOMEM;
             goto bad;
         }
-        h->bin_size = (c->max - c->min) / (MQ_BIN_NUM - 1);
-        memset(h->values, 0, sizeof h->values);
-        memset(h->counts, 0, sizeof h->counts);
-        size_t bin_start = 0;
-        for (int b = 0; b < MQ_BIN_NUM; b++) {
-            h->values[b] = (int)bin_start;
-            bin_start += (size_t)(long)h->bin_size;
-        }
-        if (h->bin_size == 0) {
-            fprintf(stderr, "libmq: build_index: column %s spans < %d values; histogram counts left 0 "
-                            "(the reference divides by zero here)\n", c->name, MQ_BIN_NUM - 1);
-        } else {
-            uint64_t counts[MQ_BIN_NUM + 1];
-            if ((rc = mq_malloc(&dh, sizeof counts)) ||
-                (rc = mq_histogram(dcol, n, c->min, h->bin_size, dh, g_stream)) ||
-                (rc = d2h(counts, dh, sizeof counts))) {
-                free(h);
-                goto bad;
-            }
-            for (int b = 0; b < MQ_BIN_NUM; b++) h->counts[b] = counts[b];
+        if ((rc = histogram_fill("build_index", c, h, dcol, n, &dh))) {
+            free(h);
+            goto bad;
         }
         c->histogram = (struct Histogram*)h;
     }
@@ -1607,8 +1616,9 @@ void build_index(Db* db) {
 }
 
 /* ------------------------------------------------------------------ */
-/* row deletes and updates (the generator's milestone 5; no reference  */
-/* counterpart: parse.c:876-960 has no branch for either command)      */
+/* row deletes, updates and inserts (the generator's milestone 5; no    */
+/* reference counterpart for delete / update: parse.c:876-960 has no    */
+/* branch for them; insert_row is the reference's one-row insert)       */
 /* ------------------------------------------------------------------ */
 
 static void dml_fail(Status* st, const char* what, const char* msg) {
@@ -1740,6 +1750,220 @@ out:
     mq_pool_free(ws);
     mq_pool_free(dh);
     if (rc) fail(ret_status, "relational_delete", rc);
+}
+
+/* relational_insert(db1.tbl5,-1,-11,-111,-1111), milestone5.py:40-78: nrows rows join the
+ * table as nrows insert_row calls (db_manager.c:164-199) would add them, and the table's
+ * clustered order and every built index are maintained. All device
+ * work, and every host allocation, is done before anything on the host changes. */
+void relational_insert(Db* db, Table* table, const int* rows, size_t nrows, Status* ret_status) {
+    if (op_begin(ret_status)) return;
+    ret_status->code = OK;
+    if (!table || !rows) {
+        dml_fail(ret_status, "relational_insert", "NULL table or rows");
+        return;
+    }
+    const size_t n = table->row_count, k = nrows, m = n + k;
+    const int ncols = (int)table->col_count;
+    if (table->col_count > 1024 || m < n || m >= ((size_t)1 << 31)) {
+        dml_fail(ret_status, "relational_insert", "more than 1024 columns or 2^31 rows");
+        return;
+    }
+    for (int j = 0; j < ncols; j++)
+        if (table->columns[j].row_count != n) {
+            dml_fail(ret_status, "relational_insert", "a column's row_count differs from the table's");
+            return;
+        }
+    if (k == 0) return;
+    if (m > table->table_length && (!db || !save_data || !start_data || table->table_length == 0)) {
+        dml_fail(ret_status, "relational_insert",
+                 "the table must grow and the server's save_data/start_data are not linked (or db is NULL)");
+        return;
+    }
+    int cc = -1; /* the column whose built clustered index orders the table */
+    for (int j = 0; j < ncols && cc < 0; j++)
+        if (table->columns[j].clustered && index_built(table->columns + j)) cc = j;
+    /* the batch column by column (each from a 16-byte boundary), and its min / max */
+    const size_t stride = (k + 3) & ~(size_t)3, batch_bytes = (size_t)(ncols ? ncols : 1) * stride * 4;
+    int32_t mn[1024], mx[1024];
+    const int32_t* dcol[1024];
+    const int32_t* dnw[1024];
+    void* dnew[1024] = {NULL};
+    void *d_batch = NULL, *d_sorted = NULL, *ws = NULL, *dh = NULL;
+    void *d_tkeys = NULL, *d_tord = NULL, *d_tins = NULL, *d_slots = NULL; /* the table's interleave */
+    void *d_sv = NULL, *d_ord = NULL, *d_ins = NULL, *d_np = NULL;         /* one index's merge */
+    void **div = NULL, **dip = NULL;  /* the maintained indexes' new arrays, per column: device, */
+    void **hiv = NULL, **hip = NULL;  /* host, */
+    void** hnew = NULL;               /* and a histogram where the column has none */
+    uint64_t bad = 0;
+    int rc = 0;
+    int32_t* hb = malloc(batch_bytes);
+    if (!hb) {
+        fail(ret_status, "relational_insert batch", MQ_ENOMEM);
+        return;
+    }
+    for (int j = 0; j < ncols; j++) {
+        int32_t lo = rows[j], hi = rows[j];
+        int32_t* dst = hb + (size_t)j * stride;
+        for (size_t i = 0; i < k; i++) {
+            const int32_t v = rows[i * (size_t)ncols + j];
+            dst[i] = v;
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+        }
+        mn[j] = lo;
+        mx[j] = hi;
+    }
+    const size_t ptrs = (size_t)(ncols ? ncols : 1);
+    if (!(div = calloc(ptrs, sizeof *div)) || !(dip = calloc(ptrs, sizeof *dip)) || !(hiv = calloc(ptrs, sizeof *hiv)) ||
+        !(hip = calloc(ptrs, sizeof *hip)) || !(hnew = calloc(ptrs, sizeof *hnew))) {
+        rc = MQ_ENOMEM;
+        goto out;
+    }
+    if ((rc = dev_alloc(&d_batch, batch_bytes)) || (rc = h2d(d_batch, hb, batch_bytes))) goto out;
+    for (int j = 0; j < ncols; j++) {
+        Column* c = table->columns + j;
+        dml_detach(c);
+        Status s = {OK, NULL};
+        if ((rc = column_device(c, &dcol[j], &s)) || (rc = dev_alloc(&dnew[j], m * 4))) goto out;
+    }
+    int merges = 0;
+    for (int j = 0; j < ncols; j++) merges += j != cc && index_built(table->columns + j);
+    const size_t wsb = mq_insert_workspace_bytes(n, k);
+    if ((cc >= 0 || merges) && (rc = dev_alloc(&ws, wsb))) goto out;
+    if ((cc >= 0 || merges) && ((rc = dev_alloc(&d_np, k * 8)))) goto out;
+    if (cc >= 0) {
+        /* sorted insert: the batch in key order (stable: mq_index_build), each key's point
+         * in the clustered index's values, one plan, every column expanded by it */
+        Column* c = table->columns + cc;
+        Status s = {OK, NULL};
+        IndexEntry* e = index_device(c->index, n, &s);
+        if (!e) {
+            rc = MQ_EHIP;
+            goto out;
+        }
+        const int32_t* ev = (const int32_t*)e->d_values;
+        const uint64_t* ep = (const uint64_t*)e->d_positions;
+        if ((rc = dev_alloc(&d_tkeys, k * 4)) || (rc = dev_alloc(&d_tord, k * 8)) || (rc = dev_alloc(&d_tins, k * 4)) ||
+            (rc = dev_alloc(&d_slots, k * 8)) || (rc = dev_alloc(&d_sorted, batch_bytes)) ||
+            (rc = dev_alloc(&div[cc], m * 4)) || (rc = dev_alloc(&dip[cc], m * 8)))
+            goto out;
+        if ((rc = mq_index_build((const int32_t*)d_batch + (size_t)cc * stride, k, (int32_t*)d_tkeys, (uint64_t*)d_tord,
+                                 g_stream)) ||
+            (rc = mq_insert_points(ev, n, (const int32_t*)d_tkeys, k, (uint32_t*)d_tins, g_stream)) ||
+            (rc = mq_insert_plan((const uint32_t*)d_tins, k, n, &bad, ws, wsb, g_stream)))
+            goto out;
+        for (int j = 0; j < ncols; j++) {
+            dnw[j] = (const int32_t*)d_sorted + (size_t)j * stride;
+            if ((rc = mq_gather_u64((const int32_t*)d_batch + (size_t)j * stride, (const uint64_t*)d_tord, k,
+                                    (int32_t*)dnw[j], g_stream)))
+                goto out;
+        }
+        if ((rc = mq_insert_columns(ws, dcol, dnw, ncols, (int32_t* const*)dnew, g_stream)) ||
+            (rc = mq_insert_slots((const uint32_t*)d_tins, (const uint64_t*)d_tord, k, (uint64_t*)d_slots, g_stream)) ||
+            /* the clustered index itself: its identity positions renumber to the identity */
+            (rc = mq_insert_slots((const uint32_t*)d_tins, NULL, k, (uint64_t*)d_np, g_stream)) ||
+            (rc = mq_insert_index(ws, ev, ep, (const int32_t*)d_tkeys, (const uint64_t*)d_np, (const uint32_t*)d_tins, k,
+                                  (int32_t*)div[cc], (uint64_t*)dip[cc], g_stream)))
+            goto out;
+    } else {
+        /* append: the old copy, then the k new values, on the device */
+        for (int j = 0; j < ncols; j++)
+            if ((n && (rc = mq_memcpy_d2d(dnew[j], dcol[j], n * 4, g_stream))) ||
+                (rc = mq_memcpy_d2d((int32_t*)dnew[j] + n, (const int32_t*)d_batch + (size_t)j * stride, k * 4, g_stream)))
+                goto out;
+    }
+    if (merges && ((rc = dev_alloc(&d_sv, k * 4)) || (rc = dev_alloc(&d_ord, k * 8)) || (rc = dev_alloc(&d_ins, k * 4))))
+        goto out;
+    for (int j = 0; j < ncols; j++) {
+        /* every other built index: its k new (value, row) entries merged in, by a plan of its own */
+        Column* c = table->columns + j;
+        if (j == cc || !index_built(c)) continue;
+        Status s = {OK, NULL};
+        IndexEntry* e = index_device(c->index, n, &s);
+        if (!e) {
+            rc = MQ_EHIP;
+            goto out;
+        }
+        const int32_t* ev = (const int32_t*)e->d_values;
+        const uint64_t* ep = (const uint64_t*)e->d_positions;
+        if ((rc = dev_alloc(&div[j], m * 4)) || (rc = dev_alloc(&dip[j], m * 8)) ||
+            (rc = mq_index_build((const int32_t*)d_batch + (size_t)j * stride, k, (int32_t*)d_sv, (uint64_t*)d_ord, g_stream)) ||
+            (rc = mq_insert_points(ev, n, (const int32_t*)d_sv, k, (uint32_t*)d_ins, g_stream)) ||
+            (rc = mq_insert_plan((const uint32_t*)d_ins, k, n, &bad, ws, wsb, g_stream)) ||
+            (rc = mq_insert_positions((const uint64_t*)d_slots, n, (const uint64_t*)d_ord, k, (uint64_t*)d_np, g_stream)) ||
+            (rc = mq_insert_index(ws, ev, ep, (const int32_t*)d_sv, (const uint64_t*)d_np, (const uint32_t*)d_tins,
+                                  cc >= 0 ? k : 0, (int32_t*)div[j], (uint64_t*)dip[j], g_stream)))
+            goto out;
+    }
+    /* the indexes' new host arrays (malloc'd, as index_one's and init_column_index's are) */
+    for (int j = 0; j < ncols; j++) {
+        if (!div[j]) continue;
+        if (!(hiv[j] = malloc(m * sizeof(int))) || !(hip[j] = malloc(m * sizeof(size_t))) ||
+            (!table->columns[j].clustered && !table->columns[j].histogram && !(hnew[j] = malloc(sizeof(MqHistogram))))) {
+            rc = MQ_ENOMEM;
+            goto out;
+        }
+        if ((rc = d2h(hiv[j], div[j], m * 4)) || (rc = d2h(hip[j], dip[j], m * 8))) goto out;
+    }
+    if ((rc = mq_stream_sync(g_stream))) goto out;
+    /* commit: capacity, the host rows (guard range forgotten first), counts, min / max, and
+     * the new device arrays as the resident copies */
+    if (m > table->table_length && grow_table(db, table, m, ret_status)) {
+        ret_status->code = ERROR;
+        goto out;
+    }
+    for (int j = 0; j < ncols; j++) {
+        Column* c = table->columns + j;
+        mq_guard_forget_range((uintptr_t)c->data, m * 4);
+        if (cc < 0)
+            memcpy(c->data + n, hb + (size_t)j * stride, k * 4);
+        else if ((rc = d2h(c->data, dnew[j], m * 4)))
+            goto out;
+        c->row_count = m;
+        c->max = c->max > mx[j] ? c->max : mx[j]; /* insert_row :193-194 */
+        c->min = c->min < mn[j] ? c->min : mn[j];
+        col_put(c, dnew[j]); /* guards the rows afresh: the copy stays trusted */
+        const int32_t* d_rows = (const int32_t*)dnew[j];
+        dnew[j] = NULL;
+        if (!div[j]) continue;
+        ColumnIndex* ix = c->index;
+        mq_guard_forget_range((uintptr_t)ix->values, n * 4);
+        mq_guard_forget_range((uintptr_t)ix->positions, n * 8);
+        free(ix->values);
+        free(ix->positions);
+        ix->values = (int*)hiv[j];
+        ix->positions = (size_t*)hip[j];
+        hiv[j] = hip[j] = NULL;
+        idx_put(ix, m, div[j], dip[j], 1); /* replaces the entry over n rows */
+        div[j] = dip[j] = NULL;
+        if (c->clustered) continue;
+        if (!c->histogram) {
+            c->histogram = (struct Histogram*)hnew[j];
+            hnew[j] = NULL;
+        }
+        if ((rc = histogram_fill("relational_insert", c, (MqHistogram*)c->histogram, d_rows, m, &dh))) goto out;
+    }
+    table->row_count = m;
+out:
+    mq_stream_sync(g_stream);
+    for (int j = 0; j < ncols; j++) {
+        mq_pool_free(dnew[j]);
+        if (div) mq_pool_free(div[j]);
+        if (dip) mq_pool_free(dip[j]);
+        if (hiv) free(hiv[j]);
+        if (hip) free(hip[j]);
+        if (hnew) free(hnew[j]);
+    }
+    free(div);
+    free(dip);
+    free(hiv);
+    free(hip);
+    free(hnew);
+    free(hb);
+    void* tmp[] = {d_batch, d_sorted, ws, dh, d_tkeys, d_tord, d_tins, d_slots, d_sv, d_ord, d_ins, d_np};
+    for (size_t i = 0; i < sizeof tmp / sizeof tmp[0]; i++) mq_pool_free(tmp[i]);
+    if (rc) fail(ret_status, "relational_insert", rc);
 }
 
 /* relational_update(db1.tbl5.col1,u1,-10), milestone5.py:127-142: one value to the

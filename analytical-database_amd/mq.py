@@ -167,6 +167,13 @@ _SIGS = {
     "mq_delete_columns": (_int, [_vp, _vp, _int, _vp, _vp]),
     "mq_delete_index": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mq_update_rows": (_int, [_vp, _u64, _vp, _u64, _i32, _vp, _vp]),
+    "mq_insert_workspace_bytes": (_sz, [_u64, _u64]),
+    "mq_insert_points": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
+    "mq_insert_plan": (_int, [_vp, _u64, _u64, C.POINTER(_u64), _vp, _sz, _vp]),
+    "mq_insert_columns": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
+    "mq_insert_index": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "mq_insert_slots": (_int, [_vp, _vp, _u64, _vp, _vp]),
+    "mq_insert_positions": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -214,7 +221,8 @@ _SIGS = {
     # load path (db_manager.h:254)
     "load_db": (None, [C.POINTER(Db), C.c_char_p, _PS]),
     "build_index": (None, [C.POINTER(Db)]),
-    # row deletes and updates (the generator's milestone 5)
+    # row deletes, updates and inserts (the generator's milestone 5)
+    "relational_insert": (None, [C.POINTER(Db), C.POINTER(Table), C.POINTER(_int), _sz, _PS]),
     "relational_delete": (None, [C.POINTER(Table), _PR, _PS]),
     "relational_update": (None, [C.POINTER(Column), _PR, _int, _PS]),
     # residency

@@ -286,6 +286,55 @@ int mq_delete_index(void* d_ws, const int32_t* d_values, const uint64_t* d_posit
 int mq_update_rows(int32_t* d_col, uint64_t n, const int32_t* d_pos, uint64_t k, int32_t value,
                    uint64_t* d_bad, void* stream);
 
+/* ---- batched row inserts ----
+ * The write path behind relational_insert (mq_query.h): the inverse of the delete. k new
+ * rows are interleaved with n old ones (n + k < 2^31); the j-th new row, in insertion
+ * order, goes in front of old row d_ins[j] (after the last one when d_ins[j] = n), and
+ * new rows with equal points keep their order. A plan and two apply steps on one
+ * workspace of mq_insert_workspace_bytes(n, k) bytes (16-byte aligned):
+ * points:  d_ins[j] (u32) = the entries of the ascending d_sorted[0, n) that are <=
+ *          d_new_sorted[j], by binary search: where a new key goes so that it follows
+ *          every old key <= it. Ascending new keys give ascending points.
+ * plan:    one bit per output slot, set for slot d_ins[j] + j (the j-th new row's), and
+ *          the count of set bits before each 64-bit word. Synchronises; *h_bad = points
+ *          that exceed n or lie below the point before them. With *h_bad != 0 it returns
+ *          MQ_EINVAL and leaves no plan. k == 0 is a valid plan that inserts nothing.
+ * columns: d_out[j][s] = bit(s) ? d_new[j][rank1(s)] : d_old[j][s - rank1(s)] for every
+ *          slot s < n + k, rank1(s) the set bits below s; d_new[j] holds the column's k new
+ *          values in insertion order; ncols <= 1024; d_old / d_new / d_out are host
+ *          arrays of device pointers, 4-byte aligned, d_out[j] distinct from both inputs.
+ *          Per column 4n + 4k bytes read, 4(n + k) written and 3(n + k)/16 of bitmap and
+ *          word counts.
+ * index:   the same expansion over a sorted index (int32 values, size_t positions) with
+ *          the new entries (d_new_values ascending, d_new_positions their rows) of a plan
+ *          made from the index's own points. With d_renumber_ins (k_renumber ascending
+ *          u32 points of the TABLE's interleave; NULL / 0 for an append) every old
+ *          position p becomes p + #{j : d_renumber_ins[j] <= p}, the row's new slot.
+ * slots:   d_slots[d_order ? d_order[j] : j] = d_ins[j] + j, the slot of every new row
+ *          filed under its batch index (d_order: the permutation that sorted the batch,
+ *          mq_index_build's positions; an entry outside [0, k) files nothing).
+ * positions: d_out[i] = d_slots ? d_slots[d_order[i]] : base + d_order[i]: the rows of the
+ *          batch entries in another sorted order (an unclustered index's new entries).
+ * The apply steps run on the insert plan the calling thread made last, on that workspace
+ * and device, are asynchronous on `stream`, and may be repeated while the workspace is
+ * untouched (a delete plan on the same workspace ends the insert plan, and the reverse).
+ * MQ_EINVAL: NULL pointers, n + k >= 2^31, a short or misaligned workspace, no plan. */
+size_t mq_insert_workspace_bytes(uint64_t n, uint64_t k);
+int mq_insert_points(const int32_t* d_sorted, uint64_t n, const int32_t* d_new_sorted, uint64_t k,
+                     uint32_t* d_ins, void* stream);
+int mq_insert_plan(const uint32_t* d_ins, uint64_t k, uint64_t n, uint64_t* h_bad, void* d_ws,
+                   size_t ws_bytes, void* stream);
+int mq_insert_columns(const void* d_ws, const int32_t* const* d_old, const int32_t* const* d_new,
+                      int ncols, int32_t* const* d_out, void* stream);
+int mq_insert_index(const void* d_ws, const int32_t* d_values, const uint64_t* d_positions,
+                    const int32_t* d_new_values, const uint64_t* d_new_positions,
+                    const uint32_t* d_renumber_ins, uint64_t k_renumber, int32_t* d_values_out,
+                    uint64_t* d_positions_out, void* stream);
+int mq_insert_slots(const uint32_t* d_ins, const uint64_t* d_order, uint64_t k, uint64_t* d_slots,
+                    void* stream);
+int mq_insert_positions(const uint64_t* d_slots, uint64_t base, const uint64_t* d_order, uint64_t k,
+                        uint64_t* d_out, void* stream);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

@@ -232,6 +232,40 @@ void build_index(Db* db);
 void relational_delete(Table* table, Result* positions, Status* ret_status);
 void relational_update(Column* column, Result* positions, int value, Status* ret_status);
 
+/* ---- batched row inserts (the workload generator's milestone 5) ----
+ * The DSL's relational_insert(db1.tbl5,-1,-11,-111,-1111). The reference declares no
+ * function of this name (it is a parser string only, parse.c:885, which calls insert_row,
+ * db_manager.c:164-199); libmq does not export insert_row, the server's db_manager.o
+ * defines it. `rows` holds nrows x table->col_count ints, row-major: nrows consecutive
+ * insert_row rows in the order they would have been issued. `db` is used only when the
+ * table must grow and may be NULL otherwise. The operator works on the columns' resident
+ * copies and leaves them resident and trusted, so the next operator
+ * uploads nothing; a column that was not resident is uploaded once first. Attached copies
+ * are detached first and never written; row shards are dropped and split again on next
+ * use. nrows == 0 changes nothing.
+ * A table without a built clustered index: the rows are appended as insert_row appends
+ *   them: host rows [n, n + nrows) of every column, row_count of the table and of every
+ *   column, max / min widened (db_manager.c:193-194). The resident copy is extended on the
+ *   device from the old copy and an upload of the new values only.
+ * A table with a built clustered index on column c stays sorted on it: row r's key is
+ *   c->index->values[r], a new row's key its value for c, and the result is the stable
+ *   sort by key of the old rows followed by the new ones (a new row lands after every old
+ *   row with key <= its own; equal new keys keep batch order). Every column (c's own data
+ *   included) and index->values are interleaved that way and written back to the host;
+ *   index->positions stays 0..n+nrows-1.
+ * Every built unclustered sorted index of the table has the new (value, row) entries
+ *   merged in, each after every entry of equal or smaller value, equal new values in batch
+ *   order; on a clustered table the old positions are renumbered to the rows' new slots
+ *   first. index->values / positions are freed and replaced by malloc'd arrays of the new
+ *   length, and the histogram is rebuilt as build_index builds it, from the widened
+ *   min / max. A column with has_index whose index was never built gets its rows only.
+ * ERROR (a "libmq:" line on stderr, nothing changed): no device, NULL table or rows, more
+ *   than 1024 columns, row_count + nrows >= 2^31, a column whose row_count differs from
+ *   the table's, a device failure, or row_count + nrows > table_length while the server's
+ *   save_data / start_data are not linked or db is NULL. With them the capacity grows as
+ *   load_db grows it: one remap to the first table_length * 2^j that fits. */
+void relational_insert(Db* db, Table* table, const int* rows, size_t nrows, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
