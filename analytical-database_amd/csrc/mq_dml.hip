@@ -109,41 +109,6 @@ struct InsPlan {
 };
 thread_local InsPlan g_iplan = {nullptr, 0, 0, -1};
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t u = __shfl_up(v, off, 64);
-        if (lane >= off) v += u;
-    }
-    return v;
-}
-
-// Exclusive prefix of v over the block's kTPB threads; *total = the block's sum.
-// s_w: kWaves words of LDS, free again when the call returns.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t inc = wave_incl_scan(v, lane);
-    __syncthreads();  // the previous call's reads of s_w are done
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t below = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; w++) {
-        const uint32_t c = s_w[w];
-        below += w < wave ? c : 0u;
-        all += c;
-    }
-    *total = all;
-    return below + inc - v;
-}
-
-// Sum of v over the block (every thread receives it).
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* s_w) {
-    uint32_t total;
-    (void)block_excl_scan(v, s_w, &total);
-    return total;
-}
-
 __global__ __launch_bounds__(kTPB) void k_dml_mark(const int32_t* __restrict__ pos, uint64_t k, uint32_t n,
                                                    uint32_t* __restrict__ bm32, u64* __restrict__ bad) {
     const uint64_t stride = (uint64_t)gridDim.x * kTPB;
@@ -541,16 +506,6 @@ __global__ __launch_bounds__(kTPB) void k_ins_positions(const u64* __restrict__ 
         const u64 o = order[i];
         out[i] = o < k ? (slots ? slots[o] : base + o) : ~0ull;
     }
-}
-
-// A fixed grid of at most max_blocks contiguous chunks, each a whole number of `step`s.
-void chunks(uint64_t items, uint64_t step, uint32_t max_blocks, uint32_t* blocks, uint64_t* chunk) {
-    const uint64_t steps = (items + step - 1) / step;
-    uint64_t per = (steps + max_blocks - 1) / max_blocks;
-    if (per == 0) per = 1;
-    *chunk = per * step;
-    *blocks = (uint32_t)((items + *chunk - 1) / *chunk);
-    if (*blocks == 0) *blocks = 1;
 }
 
 // The calling thread's plan on d_ws, or NULL.

@@ -1,0 +1,696 @@
+// mq_group.hip — grouped count / sum / min / max by an int32 key.
+//
+// n rows of (key, value), both int32, give one entry per distinct key in ascending
+// signed key order: the key, its row count (u64), the exact int64 sum of its values and
+// their min / max. The reference has no such operator; the semantics are restated in
+// numpy by tests/groupcases.py. Every combine is an integer add / min / max, so the
+// result does not depend on the order in which blocks, waves or lanes contribute.
+//
+// A plan and a write on a handle (the caller sizes the outputs from the plan's group
+// count), by one of two paths chosen from the key range hi - lo + 1 alone:
+//
+// dense (range <= kDenseSlots), one streaming read of both columns:
+//   k_group_dense      : k_scan's chunking and nt dwordx4 loads, kGrpU tiles of each
+//                        column in flight. Each block keeps a table in LDS addressed by
+//                        key - lo, as four arrays (u32 count, u64 sum, min, max: neighbouring
+//                        slots lie in neighbouring banks), updated with LDS atomics. A
+//                        wave tile (256 rows) whose keys are all equal is folded into
+//                        per-lane registers instead, and the run of such tiles is flushed
+//                        with one update when the key changes: a clustered key column and
+//                        a one-key column issue a handful of atomics per block. A key
+//                        outside [lo, hi] is counted, never used as an address. The block's
+//                        table leaves with plain stores to its own slice of the scratch.
+//   k_group_fold       : per slot, the sum over the blocks' tables (16 slots x 16 block
+//                        strides a workgroup, the strides combined through LDS).
+//   k_group_rank       : the non-empty slots' output index (one block scan) and the group
+//                        count; also the sum of the blocks' out-of-bounds counts.
+//   k_group_dense_write: non-empty slot s goes to out[rank[s]], key lo + s.
+//
+// sort (everything else): rows ordered by key with mq_index_build (sorted keys and row
+// positions, the project's one sort), then
+//   k_group_heads      : run heads (sorted[i] != sorted[i - 1]) counted per chunk of a
+//                        fixed grid; their total is the group count.
+//   k_group_seg_init   : identity into the outputs of the groups that meet a chunk edge.
+//   k_group_seg_write  : each block walks its chunk in 1024-row tiles: the rows' group
+//                        index follows from the heads before them (chunk sums below, then
+//                        ballots), values are gathered through the positions and reduced
+//                        per run in LDS. A run inside one tile is stored directly; the run
+//                        left open at a tile's end is carried to the next tile; a run that
+//                        crosses a chunk edge is combined with atomics onto the identity.
+
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+#include <new>
+
+#include "mq_common.h"
+#include "mq_device.h"
+#include "mq_scan_common.h"
+
+struct mq_group {
+    int path;
+    int dev;
+    uint64_t n, groups;
+    const int32_t* vals;
+    hipStream_t stream;  // of the last call that queued work on the buffers below
+    // dense: the folded table
+    int32_t lo;
+    uint32_t range;
+    char* tab;
+    // sort: the sorted keys, their rows, the chunks' head counts
+    int32_t* sorted;
+    unsigned long long* pos;
+    uint32_t* ccnt;
+    uint32_t blocks;
+    uint64_t chunk;
+};
+
+namespace {
+
+using namespace mqi;
+using u64 = unsigned long long;
+
+// 2048 slots x 20 B = 40 KiB of LDS a block: 4 blocks (16 waves) a CU in 160 KiB.
+constexpr uint32_t kDenseSlots = 2048;
+constexpr int kGrpU = 4;                       // tiles of each column in flight per thread
+constexpr int kFoldSlots = 16;                 // slots per fold workgroup
+constexpr int kFoldParts = kTPB / kFoldSlots;  // block strides per slot
+constexpr int kSegBlocks = 2048;               // chunks of the sort path's passes
+constexpr int kSegU = 4;                       // rows per lane per tile
+constexpr int kSegTile = kTPB * kSegU;
+
+// The blocks' tables in the scratch, [block][slot] each; bad: [block][wave].
+struct DenseTabs {
+    long long* sum;
+    uint32_t* cnt;
+    int* mn;
+    int* mx;
+    uint32_t* bad;
+};
+
+size_t dense_scratch_bytes(uint32_t blocks, uint32_t range) {
+    return (size_t)blocks * range * 20 + (size_t)blocks * kWaves * 4;
+}
+
+DenseTabs dense_tabs(void* scratch, uint32_t blocks, uint32_t range) {
+    const size_t cells = (size_t)blocks * range;
+    DenseTabs t;
+    t.sum = static_cast<long long*>(scratch);
+    t.cnt = reinterpret_cast<uint32_t*>(t.sum + cells);
+    t.mn = reinterpret_cast<int*>(t.cnt + cells);
+    t.mx = t.mn + cells;
+    t.bad = reinterpret_cast<uint32_t*>(t.mx + cells);
+    return t;
+}
+
+// The folded table in the handle: [groups u64][bad u64] then per slot count, sum, min,
+// max and the output index.
+struct FinalTab {
+    u64* hdr;
+    u64* cnt;
+    long long* sum;
+    int* mn;
+    int* mx;
+    uint32_t* rank;
+};
+
+size_t final_bytes(uint32_t range) { return 16 + (size_t)range * 28; }
+
+FinalTab final_tab(char* p, uint32_t range) {
+    FinalTab f;
+    f.hdr = reinterpret_cast<u64*>(p);
+    f.cnt = f.hdr + 2;
+    f.sum = reinterpret_cast<long long*>(f.cnt + range);
+    f.mn = reinterpret_cast<int*>(f.sum + range);
+    f.mx = f.mn + range;
+    f.rank = reinterpret_cast<uint32_t*>(f.mx + range);
+    return f;
+}
+
+template <bool VK, bool VV>
+__global__ __launch_bounds__(kTPB, 4) void k_group_dense(const int* keys, const int* vals, uint64_t n,
+                                                         uint64_t rows_per_block, int32_t lo, uint32_t range,
+                                                         DenseTabs out) {
+    __shared__ uint32_t s_cnt[kDenseSlots];
+    __shared__ u64 s_sum[kDenseSlots];
+    __shared__ int s_mn[kDenseSlots];
+    __shared__ int s_mx[kDenseSlots];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        s_cnt[s] = 0u;
+        s_sum[s] = 0ull;
+        s_mn[s] = INT_MAX;
+        s_mx[s] = INT_MIN;
+    }
+    __syncthreads();
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    uint32_t nbad = 0;
+    // the wave's run of tiles whose 256 keys all equal run_key, folded per lane
+    int run_key = 0;
+    uint32_t run_tiles = 0;
+    long long r_sum = 0;
+    int r_mn = INT_MAX, r_mx = INT_MIN;
+
+    auto update = [&](int k, int v) {
+        const uint32_t s = (uint32_t)k - (uint32_t)lo;  // a key below lo wraps past range
+        if (s < range) {
+            atomicAdd(&s_cnt[s], 1u);
+            atomicAdd(&s_sum[s], (u64)(long long)v);
+            atomicMin(&s_mn[s], v);
+            atomicMax(&s_mx[s], v);
+        } else {
+            nbad++;
+        }
+    };
+    auto flush = [&]() {  // wave-uniform
+        const long long sm = wave_sum_i64(r_sum);
+        const int mn = wave_min(r_mn), mx = wave_max(r_mx);
+        if (lane == 0) {
+            const uint32_t s = (uint32_t)run_key - (uint32_t)lo;
+            if (s < range) {
+                atomicAdd(&s_cnt[s], run_tiles * 256u);
+                atomicAdd(&s_sum[s], (u64)sm);
+                atomicMin(&s_mn[s], mn);
+                atomicMax(&s_mx[s], mx);
+            } else {
+                nbad += run_tiles * 256u;
+            }
+        }
+        run_tiles = 0;
+        r_sum = 0;
+        r_mn = INT_MAX;
+        r_mx = INT_MIN;
+    };
+    auto consume = [&](int4 k, int4 v) {  // a full tile
+        const int k0 = __builtin_amdgcn_readfirstlane(k.x);
+        if (__all(k.x == k0 && k.y == k0 && k.z == k0 && k.w == k0)) {
+            if (run_tiles && k0 != run_key) flush();
+            run_key = k0;
+            run_tiles++;
+            r_sum += (long long)v.x + (long long)v.y + (long long)v.z + (long long)v.w;
+            r_mn = min(r_mn, min(min(v.x, v.y), min(v.z, v.w)));
+            r_mx = max(r_mx, max(max(v.x, v.y), max(v.z, v.w)));
+        } else {
+            update(k.x, v.x);
+            update(k.y, v.y);
+            update(k.z, v.z);
+            update(k.w, v.w);
+        }
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)kGrpU * kTileRows <= end; t += (uint64_t)kGrpU * kTileRows) {
+        int4 k[kGrpU], v[kGrpU];
+#pragma unroll
+        for (int u = 0; u < kGrpU; u++) k[u] = load4_nt<VK>(keys + t + (uint64_t)u * kTileRows + (uint64_t)tid * 4);
+#pragma unroll
+        for (int u = 0; u < kGrpU; u++) v[u] = load4_nt<VV>(vals + t + (uint64_t)u * kTileRows + (uint64_t)tid * 4);
+#pragma unroll
+        for (int u = 0; u < kGrpU; u++) consume(k[u], v[u]);
+    }
+    for (; t < end; t += kTileRows) {  // the chunk's tail
+        const uint64_t row = t + (uint64_t)tid * 4;
+        if (t + kTileRows <= end) {    // block-uniform
+            consume(load4_nt<VK>(keys + row), load4_nt<VV>(vals + row));
+        } else {                       // the last ragged tile: row by row, none past the end
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (row + e < end) update(keys[row + e], vals[row + e]);
+        }
+    }
+    if (run_tiles) flush();
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) out.bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * range;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        out.cnt[base + s] = s_cnt[s];
+        out.sum[base + s] = (long long)s_sum[s];
+        out.mn[base + s] = s_mn[s];
+        out.mx[base + s] = s_mx[s];
+    }
+}
+
+__global__ __launch_bounds__(kTPB) void k_group_fold(DenseTabs in, uint32_t blocks, uint32_t range, FinalTab f) {
+    __shared__ u64 p_cnt[kFoldParts][kFoldSlots];
+    __shared__ long long p_sum[kFoldParts][kFoldSlots];
+    __shared__ int p_mn[kFoldParts][kFoldSlots];
+    __shared__ int p_mx[kFoldParts][kFoldSlots];
+    const uint32_t sl = threadIdx.x % kFoldSlots, part = threadIdx.x / kFoldSlots;
+    const uint32_t s = blockIdx.x * kFoldSlots + sl;
+    u64 c = 0;
+    long long sm = 0;
+    int mn = INT_MAX, mx = INT_MIN;
+    if (s < range)
+        for (uint32_t b = part; b < blocks; b += kFoldParts) {
+            const size_t i = (size_t)b * range + s;
+            c += in.cnt[i];
+            sm += in.sum[i];
+            mn = min(mn, in.mn[i]);
+            mx = max(mx, in.mx[i]);
+        }
+    p_cnt[part][sl] = c;
+    p_sum[part][sl] = sm;
+    p_mn[part][sl] = mn;
+    p_mx[part][sl] = mx;
+    __syncthreads();
+    if (part == 0 && s < range) {
+        for (int p = 1; p < kFoldParts; p++) {
+            c += p_cnt[p][sl];
+            sm += p_sum[p][sl];
+            mn = min(mn, p_mn[p][sl]);
+            mx = max(mx, p_mx[p][sl]);
+        }
+        f.cnt[s] = c;
+        f.sum[s] = sm;
+        f.mn[s] = mn;
+        f.mx[s] = mx;
+    }
+}
+
+// One block: rank[s] = non-empty slots below s, hdr[0] = their number, hdr[1] = the keys
+// the blocks found outside the bounds.
+__global__ __launch_bounds__(kTPB) void k_group_rank(FinalTab f, uint32_t range, const uint32_t* __restrict__ bad,
+                                                     uint32_t nbad) {
+    __shared__ uint32_t s_w[kWaves];
+    constexpr uint32_t kPer = kDenseSlots / kTPB;
+    const uint32_t s0 = threadIdx.x * kPer;
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t e = 0; e < kPer; e++) c += s0 + e < range && f.cnt[s0 + e] != 0;
+    uint32_t total;
+    uint32_t r = block_excl_scan(c, s_w, &total);
+#pragma unroll
+    for (uint32_t e = 0; e < kPer; e++)
+        if (s0 + e < range) {
+            f.rank[s0 + e] = r;
+            r += f.cnt[s0 + e] != 0;
+        }
+    u64 b = 0;
+    for (uint32_t i = threadIdx.x; i < nbad; i += kTPB) b += bad[i];
+    b = wave_sum_u64(b);
+    __shared__ u64 s_b[kWaves];
+    if ((threadIdx.x & 63) == 0) s_b[threadIdx.x >> 6] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        f.hdr[0] = total;
+        f.hdr[1] = s_b[0] + s_b[1] + s_b[2] + s_b[3];
+    }
+}
+
+__global__ __launch_bounds__(kTPB) void k_group_dense_write(FinalTab f, uint32_t range, int32_t lo,
+                                                            int32_t* __restrict__ keys_out, u64* __restrict__ count_out,
+                                                            long long* __restrict__ sum_out, int32_t* __restrict__ min_out,
+                                                            int32_t* __restrict__ max_out) {
+    const uint32_t s = blockIdx.x * kTPB + threadIdx.x;
+    if (s >= range) return;
+    const u64 c = f.cnt[s];
+    if (c == 0) return;
+    const uint32_t o = f.rank[s];  // < the group count the plan returned
+    if (keys_out) keys_out[o] = (int32_t)((uint32_t)lo + s);
+    if (count_out) count_out[o] = c;
+    if (sum_out) sum_out[o] = f.sum[s];
+    if (min_out) min_out[o] = f.mn[s];
+    if (max_out) max_out[o] = f.mx[s];
+}
+
+// ---- the sort path ----
+
+// ccnt[b] = run heads in block b's chunk of the sorted keys; *groups = their total.
+__global__ __launch_bounds__(kTPB) void k_group_heads(const int32_t* __restrict__ sorted, uint32_t n, uint64_t chunk,
+                                                      uint32_t* __restrict__ ccnt, u64* __restrict__ groups) {
+    __shared__ uint32_t s_w[kWaves];
+    const uint64_t i0 = (uint64_t)blockIdx.x * chunk;
+    const uint64_t i1 = i0 + chunk < n ? i0 + chunk : n;
+    uint32_t c = 0;
+    for (uint64_t i = i0 + threadIdx.x; i < i1; i += kTPB) c += i == 0 || sorted[i] != sorted[i - 1];
+    const uint32_t total = block_sum(c, s_w);
+    if (threadIdx.x == 0) {
+        ccnt[blockIdx.x] = total;
+        if (total) atomicAdd(groups, (u64)total);
+    }
+}
+
+struct GroupOut {
+    int32_t* keys;
+    u64* count;
+    long long* sum;
+    int32_t* mn;
+    int32_t* mx;
+    u64 groups;
+};
+
+// One block. The group open at the end of chunk b, the last of the heads in chunks 0..b,
+// is the only one that rows of several chunks can belong to: it receives the identity.
+__global__ __launch_bounds__(kTPB) void k_group_seg_init(const uint32_t* __restrict__ ccnt, uint32_t blocks, GroupOut o) {
+    __shared__ uint32_t s_w[kWaves];
+    u64 run = 0;
+    for (uint32_t b0 = 0; b0 < blocks; b0 += kTPB) {  // block-uniform trip count
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t v = b < blocks ? ccnt[b] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_excl_scan(v, s_w, &total);
+        const u64 incl = run + ex + v;
+        if (b < blocks && incl > 0 && incl <= o.groups) {
+            const u64 g = incl - 1;
+            if (o.count) o.count[g] = 0ull;
+            if (o.sum) o.sum[g] = 0ll;
+            if (o.mn) o.mn[g] = INT_MAX;
+            if (o.mx) o.mx[g] = INT_MIN;
+        }
+        run += total;
+    }
+}
+
+struct Run {  // one run's aggregate while it is open
+    u64 cnt;
+    long long sum;
+    int mn, mx;
+};
+
+__device__ __forceinline__ void emit_run(const GroupOut& o, u64 g, const Run& r, bool atomic) {
+    if (g >= o.groups) return;  // never: g counts heads, the plan counted the same heads
+    if (atomic) {
+        if (o.count) atomicAdd(o.count + g, r.cnt);
+        if (o.sum) atomicAdd(reinterpret_cast<u64*>(o.sum) + g, (u64)r.sum);
+        if (o.mn) atomicMin(o.mn + g, r.mn);
+        if (o.mx) atomicMax(o.mx + g, r.mx);
+    } else {
+        if (o.count) o.count[g] = r.cnt;
+        if (o.sum) o.sum[g] = r.sum;
+        if (o.mn) o.mn[g] = r.mn;
+        if (o.mx) o.mx[g] = r.mx;
+    }
+}
+
+// Row i of the sorted keys belongs to group (heads in [0, i]) - 1. Within a tile, local
+// slot l = heads in the tile up to and including the row: slot 0 continues the run open
+// before the tile, slot nh (the tile's head count) is open at its end.
+__global__ __launch_bounds__(kTPB) void k_group_seg_write(const int32_t* __restrict__ sorted, const u64* __restrict__ pos,
+                                                          const int32_t* __restrict__ vals, uint32_t n, uint64_t chunk,
+                                                          const uint32_t* __restrict__ ccnt, int need_vals, GroupOut o) {
+    __shared__ uint32_t s_c[kSegTile + 1];
+    __shared__ u64 s_s[kSegTile + 1];
+    __shared__ int s_mn[kSegTile + 1];
+    __shared__ int s_mx[kSegTile + 1];
+    __shared__ uint32_t s_w[kWaves];
+    __shared__ uint32_t s_hc[kSegU][kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t below = 0;
+    for (uint32_t i = tid; i < blockIdx.x; i += kTPB) below += ccnt[i];
+    u64 base = block_sum(below, s_w);  // heads before the tile (< 2^31)
+    const uint64_t i0 = (uint64_t)blockIdx.x * chunk;
+    const uint64_t i1 = i0 + chunk < n ? i0 + chunk : n;
+    // thread 0 keeps the open run: its group, and whether it began before this chunk
+    Run car = {0ull, 0ll, INT_MAX, INT_MIN};
+    u64 car_g = 0;
+    bool car_valid = false, car_left = false;
+    for (uint64_t s = i0; s < i1; s += kSegTile) {  // block-uniform trip count
+        for (uint32_t q = tid; q <= (uint32_t)kSegTile; q += kTPB) {
+            s_c[q] = 0u;
+            s_s[q] = 0ull;
+            s_mn[q] = INT_MAX;
+            s_mx[q] = INT_MIN;
+        }
+        int32_t k[kSegU], v[kSegU];
+        u64 p[kSegU];
+        bool ok[kSegU], h[kSegU];
+#pragma unroll
+        for (int u = 0; u < kSegU; u++) {
+            const uint64_t i = s + (uint64_t)u * kTPB + tid;
+            ok[u] = i < i1;
+            k[u] = ok[u] ? sorted[i] : 0;
+            h[u] = ok[u] && (i == 0 || k[u] != sorted[i - 1]);
+            p[u] = ok[u] && need_vals ? pos[i] : ~0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < kSegU; u++) v[u] = p[u] < n ? vals[p[u]] : 0;
+        uint32_t in_wave[kSegU];
+#pragma unroll
+        for (int u = 0; u < kSegU; u++) {
+            const u64 m = __ballot(h[u]);
+            in_wave[u] = lanes_below(m);
+            if (lane == 0) s_hc[u][wave] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();  // the slots are initialised, the head counts are in
+        uint32_t nh = 0;
+#pragma unroll
+        for (int u = 0; u < kSegU; u++) {
+            uint32_t mine = nh;
+#pragma unroll
+            for (int w = 0; w < kWaves; w++) {
+                const uint32_t c = s_hc[u][w];
+                mine += w < wave ? c : 0u;
+                nh += c;
+            }
+            if (!ok[u]) continue;
+            const uint32_t l = mine + in_wave[u] + (h[u] ? 1u : 0u);  // <= rows before + 1 <= kSegTile
+            atomicAdd(&s_c[l], 1u);
+            if (need_vals) {
+                atomicAdd(&s_s[l], (u64)(long long)v[u]);
+                atomicMin(&s_mn[l], v[u]);
+                atomicMax(&s_mx[l], v[u]);
+            }
+            if (h[u] && o.keys && base + l - 1 < o.groups) o.keys[base + l - 1] = k[u];
+        }
+        __syncthreads();
+        for (uint32_t q = 1 + tid; q < nh; q += kTPB)  // runs that begin and end in this tile
+            emit_run(o, base + q - 1, Run{s_c[q], (long long)s_s[q], s_mn[q], s_mx[q]}, false);
+        if (tid == 0) {
+            if (s_c[0]) {  // rows of the run open before the tile
+                if (!car_valid) {  // the chunk's first tile, whose first row is no head
+                    car_valid = car_left = true;
+                    car_g = base - 1;
+                }
+                car.cnt += s_c[0];
+                car.sum += (long long)s_s[0];
+                car.mn = min(car.mn, s_mn[0]);
+                car.mx = max(car.mx, s_mx[0]);
+            }
+            if (nh) {  // a head closed it; the tile's last run is open now
+                if (car_valid) emit_run(o, car_g, car, car_left);
+                car = Run{s_c[nh], (long long)s_s[nh], s_mn[nh], s_mx[nh]};
+                car_g = base + nh - 1;
+                car_valid = true;
+                car_left = false;
+            }
+        }
+        base += nh;
+        __syncthreads();  // the slots are read before the next tile resets them
+    }
+    if (tid == 0 && car_valid) emit_run(o, car_g, car, true);  // may go on in the next chunk
+}
+
+template <bool VK, bool VV>
+int launch_dense(const DevState* s, const int32_t* keys, const int32_t* vals, uint64_t n, int32_t lo, uint32_t range,
+                 void** scratch_out, DenseTabs* tabs, uint32_t* blocks_out, hipStream_t st) {
+    uint32_t g;
+    uint64_t rpb;
+    geometry(s, n, reinterpret_cast<const void*>(&k_group_dense<VK, VV>), &g, &rpb);
+    void* scratch = pool_alloc(dense_scratch_bytes(g, range));
+    if (!scratch) return set_err(MQ_ENOMEM, "mq_group_plan: scratch allocation failed");
+    *tabs = dense_tabs(scratch, g, range);
+    *scratch_out = scratch;
+    *blocks_out = g;
+    hipLaunchKernelGGL((k_group_dense<VK, VV>), dim3(g), dim3(kTPB), 0, st, keys, vals, n, rpb, lo, range, *tabs);
+    LAUNCHCHK("k_group_dense");
+    return MQ_OK;
+}
+
+int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_t* vals, uint64_t n, hipStream_t st) {
+    g->tab = static_cast<char*>(pool_alloc(final_bytes(g->range)));
+    if (!g->tab) return set_err(MQ_ENOMEM, "mq_group_plan: table allocation failed");
+    const FinalTab f = final_tab(g->tab, g->range);
+    void* scratch = nullptr;
+    DenseTabs tabs;
+    uint32_t blocks = 0;
+    const bool vk = aligned16(keys), vv = aligned16(vals);
+    int rc = vk ? (vv ? launch_dense<true, true>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
+                      : launch_dense<true, false>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st))
+                : (vv ? launch_dense<false, true>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
+                      : launch_dense<false, false>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st));
+    if (rc) {
+        pool_free_on(scratch, st);
+        return rc;
+    }
+    hipLaunchKernelGGL(k_group_fold, dim3((g->range + kFoldSlots - 1) / kFoldSlots), dim3(kTPB), 0, st, tabs, blocks,
+                       g->range, f);
+    hipLaunchKernelGGL(k_group_rank, dim3(1), dim3(kTPB), 0, st, f, g->range, tabs.bad, blocks * kWaves);
+    const hipError_t e = hipGetLastError();
+    pool_free_on(scratch, st);  // the two kernels queued above are its last readers
+    if (e != hipSuccess) return set_err(MQ_EHIP, "launch of k_group_fold / k_group_rank failed: %s", hipGetErrorString(e));
+    u64 h[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(h, f.hdr, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[1]) return set_err(MQ_EINVAL, "mq_group_plan: %llu keys outside the bounds [%d, %lld]", h[1], g->lo,
+                             (long long)g->lo + g->range - 1);
+    g->groups = h[0];
+    return MQ_OK;
+}
+
+int plan_sort(mq_group* g, const int32_t* keys, uint64_t n, const int32_t* bounds, hipStream_t st) {
+    g->sorted = static_cast<int32_t*>(pool_alloc(n * 4));
+    g->pos = static_cast<u64*>(pool_alloc(n * 8));
+    g->ccnt = static_cast<uint32_t*>(pool_alloc(16 + (size_t)kSegBlocks * 4));  // [groups u64][pad] then the counts
+    if (!g->sorted || !g->pos || !g->ccnt) return set_err(MQ_ENOMEM, "mq_group_plan: allocation failed");
+    int rc = mq_index_build(keys, n, g->sorted, reinterpret_cast<uint64_t*>(g->pos), st);  // synchronises
+    if (rc) return rc;
+    if (bounds) {
+        int32_t ends[2];
+        HIPCHK(hipMemcpyAsync(&ends[0], g->sorted, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&ends[1], g->sorted + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (ends[0] < bounds[0] || ends[1] > bounds[1])
+            return set_err(MQ_EINVAL, "mq_group_plan: keys [%d, %d] outside the bounds [%d, %d]", ends[0], ends[1], bounds[0],
+                           bounds[1]);
+    }
+    chunks(n, kSegTile, kSegBlocks, &g->blocks, &g->chunk);
+    u64* hdr = reinterpret_cast<u64*>(g->ccnt);
+    HIPCHK(hipMemsetAsync(hdr, 0, 16, st));
+    hipLaunchKernelGGL(k_group_heads, dim3(g->blocks), dim3(kTPB), 0, st, g->sorted, (uint32_t)n, g->chunk, g->ccnt + 4, hdr);
+    LAUNCHCHK("k_group_heads");
+    u64 groups = 0;
+    HIPCHK(hipMemcpyAsync(&groups, hdr, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    g->groups = groups;
+    return MQ_OK;
+}
+
+void release(mq_group* g, hipStream_t st) {
+    pool_free_on(g->tab, st);
+    pool_free_on(g->sorted, st);
+    pool_free_on(g->pos, st);
+    pool_free_on(g->ccnt, st);
+    delete g;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t mq_group_dense_slots(void) { return kDenseSlots; }
+
+int mq_group_plan(const int32_t* d_keys, const int32_t* d_vals, uint64_t n, const int32_t* h_key_bounds, int path,
+                  mq_group** out, uint64_t* h_groups, int* h_path, void* stream) {
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (out) *out = nullptr;
+    if (h_groups) *h_groups = 0;
+    if (!out || !h_groups || (n && (!d_keys || !d_vals))) return set_err(MQ_EINVAL, "mq_group_plan: NULL pointer");
+    if (path != MQ_GROUP_AUTO && path != MQ_GROUP_DENSE && path != MQ_GROUP_SORT)
+        return set_err(MQ_EINVAL, "mq_group_plan: path %d", path);
+    if (n >= (1ull << 31)) return set_err(MQ_EINVAL, "mq_group_plan: n >= 2^31");
+    if ((reinterpret_cast<uintptr_t>(d_keys) & 3u) || (reinterpret_cast<uintptr_t>(d_vals) & 3u))
+        return set_err(MQ_EINVAL, "mq_group_plan: column not 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    mq_group* g = new (std::nothrow) mq_group();
+    if (!g) return set_err(MQ_ENOMEM, "mq_group_plan: out of host memory");
+    g->dev = dev;
+    g->n = n;
+    g->vals = d_vals;
+    g->stream = st;
+    if (n == 0) {
+        g->path = path == MQ_GROUP_SORT ? MQ_GROUP_SORT : MQ_GROUP_DENSE;
+        if (h_path) *h_path = g->path;
+        *out = g;
+        return MQ_OK;
+    }
+    int32_t lo, hi;
+    if (h_key_bounds) {
+        lo = h_key_bounds[0];
+        hi = h_key_bounds[1];
+        if (lo > hi) {
+            delete g;
+            return set_err(MQ_EINVAL, "mq_group_plan: bounds [%d, %d] are empty", lo, hi);
+        }
+    } else {  // one more read of the keys
+        char* ws = static_cast<char*>(pool_alloc(partial_bytes() + sizeof(mq_agg)));
+        if (!ws) {
+            delete g;
+            return set_err(MQ_ENOMEM, "mq_group_plan: workspace allocation failed");
+        }
+        mq_agg a = {};
+        mq_agg* d_agg = reinterpret_cast<mq_agg*>(ws + partial_bytes());
+        rc = mq_reduce(d_keys, n, d_agg, ws, partial_bytes(), stream);
+        if (!rc && hipMemcpyAsync(&a, d_agg, sizeof a, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "mq_group_plan: bounds download failed");
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "mq_group_plan: stream failed");
+        pool_free(ws);
+        if (rc) {
+            delete g;
+            return rc;
+        }
+        lo = a.min;
+        hi = a.max;
+    }
+    const int64_t range = (int64_t)hi - (int64_t)lo + 1;  // up to 2^32
+    if (path == MQ_GROUP_DENSE && range > (int64_t)kDenseSlots) {
+        delete g;
+        return set_err(MQ_EINVAL, "mq_group_plan: key range %lld exceeds the dense path's %u slots", (long long)range,
+                       kDenseSlots);
+    }
+    g->path = path != MQ_GROUP_AUTO ? path : range <= (int64_t)kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
+    if (g->path == MQ_GROUP_DENSE) {
+        g->lo = lo;
+        g->range = (uint32_t)range;
+        rc = plan_dense(s, g, d_keys, d_vals, n, st);
+    } else {
+        rc = plan_sort(g, d_keys, n, h_key_bounds, st);
+    }
+    if (rc) {
+        release(g, st);
+        return rc;
+    }
+    if (h_path) *h_path = g->path;
+    *h_groups = g->groups;
+    *out = g;
+    return MQ_OK;
+}
+
+int mq_group_write(mq_group* g, int32_t* d_keys_out, uint64_t* d_count_out, int64_t* d_sum_out, int32_t* d_min_out,
+                   int32_t* d_max_out, void* stream) {
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (!g) return set_err(MQ_EINVAL, "mq_group_write: NULL handle");
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    if (dev != g->dev) return set_err(MQ_EINVAL, "mq_group_write: the plan was made on device %d", g->dev);
+    if (g->groups == 0) return MQ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    g->stream = st;
+    u64* cnt = reinterpret_cast<u64*>(d_count_out);
+    long long* sum = reinterpret_cast<long long*>(d_sum_out);
+    if (g->path == MQ_GROUP_DENSE) {
+        hipLaunchKernelGGL(k_group_dense_write, dim3((g->range + kTPB - 1) / kTPB), dim3(kTPB), 0, st,
+                           final_tab(g->tab, g->range), g->range, g->lo, d_keys_out, cnt, sum, d_min_out, d_max_out);
+        LAUNCHCHK("k_group_dense_write");
+        return MQ_OK;
+    }
+    const GroupOut o = {d_keys_out, cnt, sum, d_min_out, d_max_out, g->groups};
+    const int need_vals = d_sum_out || d_min_out || d_max_out;
+    hipLaunchKernelGGL(k_group_seg_init, dim3(1), dim3(kTPB), 0, st, g->ccnt + 4, g->blocks, o);
+    LAUNCHCHK("k_group_seg_init");
+    hipLaunchKernelGGL(k_group_seg_write, dim3(g->blocks), dim3(kTPB), 0, st, g->sorted, g->pos, g->vals, (uint32_t)g->n,
+                       g->chunk, g->ccnt + 4, need_vals, o);
+    LAUNCHCHK("k_group_seg_write");
+    return MQ_OK;
+}
+
+int mq_group_free(mq_group* g) {
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (!g) return MQ_OK;
+    release(g, g->stream);  // a queued write may still read the buffers: freed in its stream's order
+    return MQ_OK;
+}
+
+}  // extern "C"

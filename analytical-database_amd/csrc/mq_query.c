@@ -169,6 +169,7 @@ static int fail(Status* st, const char* what, int rc) {
 }
 
 static void sweep(void);
+static void dml_fail(Status* st, const char* what, const char* msg);
 
 static int ready(Status* st) {
     if (g_ready == 1) return 0;
@@ -1054,6 +1055,99 @@ Result** hash_join(Result* column_one, Result* position_one, Result* column_two,
         result_device(column_two, &d2, ret_status) || result_device(position_two, &dp2, ret_status))
         return NULL;
     return join_pairs(d1, dp1, column_one->num_tuples, d2, dp2, column_two->num_tuples, 0, ret_status);
+}
+
+/* The int32 rows behind one argument of group_aggregate on the calling device: a
+ * Column's resident copy (row shards are dropped first: the operator runs on one device)
+ * or an INT Result's shadow. */
+static int gcol_device(GeneralizedColumn* gc, const int32_t** d, size_t* n, Status* st) {
+    if (gc->column_type == COLUMN) {
+        Column* c = gc->column_pointer.column;
+        if (!c || (c->row_count && !c->data)) return -1;
+        if (shard_wants(c)) shard_forget_column(c);
+        *n = c->row_count;
+        return column_device(c, d, st) ? 1 : 0;
+    }
+    if (gc->column_type != RESULT) return -1;
+    const Result* r = gc->column_pointer.result;
+    if (!r || r->data_type != INT || (r->num_tuples && !r->payload)) return -1;
+    *n = r->num_tuples;
+    return result_device(r, d, st) ? 1 : 0;
+}
+
+/* A LONG Result from n 8-byte values on the device. No shadow is kept: no operator reads
+ * a LONG Result on the device. */
+static Result* long_result_from_device(const void* d_src, size_t n, Status* st) {
+    void* host = payload_alloc(n * sizeof(long));
+    int rc = host ? 0 : MQ_ENOMEM;
+    if (!rc && n) rc = d2h(host, d_src, n * sizeof(long));
+    if (rc) {
+        free(host);
+        fail(st, "result download", rc);
+        return NULL;
+    }
+    return new_result(LONG, n, host);
+}
+
+/* Grouped count / sum / min / max of `values` by `keys` (no reference counterpart;
+ * DESIGN.md §3.11): five Results of one entry per distinct key, in ascending key order:
+ * keys (INT), count (LONG), sum (LONG), min (INT), max (INT). */
+Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const int32_t *dk = NULL, *dv = NULL;
+    size_t n = 0, nv = 0;
+    int bad = !keys || !values;
+    if (!bad) {
+        const int a = gcol_device(keys, &dk, &n, ret_status);
+        if (a > 0) return NULL;
+        const int b = a ? a : gcol_device(values, &dv, &nv, ret_status);
+        if (b > 0) return NULL;
+        bad = a < 0 || b < 0;
+    }
+    if (bad || n != nv) {
+        dml_fail(ret_status, "group_aggregate",
+                 bad ? "keys and values must each be a Column or an INT Result" : "keys and values differ in length");
+        return NULL;
+    }
+    mq_group* g = NULL;
+    uint64_t groups = 0;
+    void* buf = NULL;
+    int rc = mq_group_plan(dk, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, g_stream);
+    /* one block: count and sum (8 bytes an entry) first, then keys, min and max */
+    if (!rc) rc = dev_alloc(&buf, groups ? (size_t)groups * 28 : 16);
+    uint64_t* d_count = (uint64_t*)buf;
+    int64_t* d_sum = (int64_t*)(d_count + groups);
+    int32_t* d_keys = (int32_t*)(d_sum + groups);
+    int32_t *d_min = d_keys + groups, *d_max = d_min + groups;
+    if (!rc) rc = mq_group_write(g, d_keys, d_count, d_sum, d_min, d_max, g_stream);
+    mq_group_free(g); /* in g_stream's order, behind the write */
+    if (rc) {
+        mq_stream_sync(g_stream);
+        mq_pool_free(buf);
+        fail(ret_status, "group_aggregate", rc);
+        return NULL;
+    }
+    Result** out = (Result**)calloc(5, sizeof(Result*));
+    out[0] = int_result_from_device(d_keys, (size_t)groups, ret_status);
+    out[1] = long_result_from_device(d_count, (size_t)groups, ret_status);
+    out[2] = long_result_from_device(d_sum, (size_t)groups, ret_status);
+    out[3] = int_result_from_device(d_min, (size_t)groups, ret_status);
+    out[4] = int_result_from_device(d_max, (size_t)groups, ret_status);
+    mq_stream_sync(g_stream);
+    mq_pool_free(buf);
+    for (int i = 0; i < 5; i++)
+        if (!out[i]) {
+            for (int j = 0; j < 5; j++)
+                if (out[j]) {
+                    free(out[j]->payload);
+                    free(out[j]);
+                }
+            free(out);
+            ret_status->code = ERROR;
+            return NULL;
+        }
+    ret_status->code = OK;
+    return out;
 }
 
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner

@@ -78,6 +78,51 @@ __device__ __forceinline__ int4 load4_nt(const int* __restrict__ p) {
     }
 }
 
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t u = __shfl_up(v, off, 64);
+        if (lane >= off) v += u;
+    }
+    return v;
+}
+
+// Exclusive prefix of v over the block's kTPB threads; *total = the block's sum.
+// s_w: kWaves words of LDS, free again when the call returns.
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, uint32_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t inc = wave_incl_scan(v, lane);
+    __syncthreads();  // the previous call's reads of s_w are done
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t below = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; w++) {
+        const uint32_t c = s_w[w];
+        below += w < wave ? c : 0u;
+        all += c;
+    }
+    *total = all;
+    return below + inc - v;
+}
+
+// Sum of v over the block (every thread receives it).
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* s_w) {
+    uint32_t total;
+    (void)block_excl_scan(v, s_w, &total);
+    return total;
+}
+
+// A fixed grid of at most max_blocks contiguous chunks, each a whole number of `step`s.
+inline void chunks(uint64_t items, uint64_t step, uint32_t max_blocks, uint32_t* blocks, uint64_t* chunk) {
+    const uint64_t steps = (items + step - 1) / step;
+    uint64_t per = (steps + max_blocks - 1) / max_blocks;
+    if (per == 0) per = 1;
+    *chunk = per * step;
+    *blocks = (uint32_t)((items + *chunk - 1) / *chunk);
+    if (*blocks == 0) *blocks = 1;
+}
+
 // Per-mode tiles in flight and occupancy target (waves per SIMD): 8 waves/SIMD
 // means <= 64 VGPRs, chosen where it fits without spills.
 

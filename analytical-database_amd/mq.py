@@ -23,6 +23,7 @@ MQ_OK, MQ_ENODEV, MQ_EINVAL, MQ_EHIP, MQ_ENOMEM, MQ_ECAP = 0, -1, -2, -3, -4, -5
 INT, LONG, FLOAT, DOUBLE = 0, 1, 2, 3
 OK, ERROR = 0, 1
 RESULT, COLUMN = 0, 1
+MQ_GROUP_AUTO, MQ_GROUP_DENSE, MQ_GROUP_SORT = 0, 1, 2
 
 
 class MqAgg(C.Structure):
@@ -174,6 +175,10 @@ _SIGS = {
     "mq_insert_index": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "mq_insert_slots": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_insert_positions": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
+    "mq_group_dense_slots": (C.c_uint32, []),
+    "mq_group_plan": (_int, [_vp, _vp, _u64, _vp, _int, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_int), _vp]),
+    "mq_group_write": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mq_group_free": (_int, [_vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -216,6 +221,7 @@ _SIGS = {
     "shared_select": (C.POINTER(_PR), [C.POINTER(SelectOperator), _int, C.POINTER(Column), _PS]),
     "nested_loop_join": (C.POINTER(_PR), [_PR, _PR, _PR, _PR, _PS]),
     "hash_join": (C.POINTER(_PR), [_PR, _PR, _PR, _PR, _PS]),
+    "group_aggregate": (C.POINTER(_PR), [C.POINTER(GeneralizedColumn), C.POINTER(GeneralizedColumn), _PS]),
     "log_result": (None, [_PR]),
     "should_use_index": (C.c_bool, [C.POINTER(Column), _int, _int]),
     # load path (db_manager.h:254)

@@ -335,6 +335,38 @@ int mq_insert_slots(const uint32_t* d_ins, const uint64_t* d_order, uint64_t k, 
 int mq_insert_positions(const uint64_t* d_slots, uint64_t base, const uint64_t* d_order, uint64_t k,
                         uint64_t* d_out, void* stream);
 
+/* ---- grouped aggregates by an int32 key ----
+ * n < 2^31 rows of (d_keys[i], d_vals[i]) give one entry per distinct key, in ascending
+ * signed key order: the key, its row count, the exact int64 sum of its values and their
+ * min / max. The reference has no such operator. d_vals may equal d_keys. Integer adds,
+ * mins and maxes only: the result is bitwise the same whatever the path, the grid or the
+ * order in which blocks finish. A plan and a write on a handle:
+ * plan:  h_key_bounds is NULL or a host {lo, hi} pair, inclusive, that may be wider than
+ *        the keys; NULL costs one more read of the keys (mq_reduce). The key range
+ *        hi - lo + 1 (64-bit: up to 2^32) picks the path under MQ_GROUP_AUTO: at most
+ *        mq_group_dense_slots() takes the dense path (one streaming read of both columns,
+ *        a table in LDS per block), anything wider the sort path (mq_index_build, then a
+ *        segmented fold through the positions). Synchronises; *h_groups = the number of
+ *        distinct keys, *h_path (may be NULL) the path taken. n == 0 gives zero groups.
+ *        MQ_EINVAL, with *h_groups = 0 and *out = NULL: a key outside the given bounds,
+ *        lo > hi with n > 0, MQ_GROUP_DENSE forced on a wider range, n >= 2^31, NULL or
+ *        misaligned columns. d_vals must stay valid until the write has run.
+ * write: the *h_groups entries into the outputs (capacity *h_groups each; nothing is
+ *        written at or past it). Any of the pointers may be NULL: that output is not
+ *        wanted. Asynchronous on `stream`, on the plan's device; may be repeated.
+ * free:  releases the handle; its buffers are freed in the order of the stream that the
+ *        last write was queued on. */
+enum { MQ_GROUP_AUTO = 0, MQ_GROUP_DENSE = 1, MQ_GROUP_SORT = 2 };
+typedef struct mq_group mq_group;
+uint32_t mq_group_dense_slots(void);   /* a constant; needs no device */
+int mq_group_plan(const int32_t* d_keys, const int32_t* d_vals, uint64_t n,
+                  const int32_t* h_key_bounds, int path, mq_group** out,
+                  uint64_t* h_groups, int* h_path, void* stream);
+int mq_group_write(mq_group* g, int32_t* d_keys_out, uint64_t* d_count_out,
+                   int64_t* d_sum_out, int32_t* d_min_out, int32_t* d_max_out,
+                   void* stream);
+int mq_group_free(mq_group* g);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

@@ -266,6 +266,22 @@ void relational_update(Column* column, Result* positions, int value, Status* ret
  *   load_db grows it: one remap to the first table_length * 2^j that fits. */
 void relational_insert(Db* db, Table* table, const int* rows, size_t nrows, Status* ret_status);
 
+/* ---- grouped aggregates (not in the reference) ----
+ * group_aggregate: count, sum, min and max of `values` per distinct value of `keys`
+ * (mq_group_plan / mq_group_write in mq_device.h). Each argument is a
+ * COLUMN or an INT RESULT (a fetch_column's output, say), as sum takes them; the two must
+ * be equally long and may be the same object. Returns a malloc'd array of five Result*,
+ * each with one tuple per distinct key, in ascending key order, and a malloc'd payload the
+ * caller frees (the hash_join contract): [0] the keys (INT), [1] the row counts (LONG),
+ * [2] the exact sums (LONG), [3] the minima (INT), [4] the maxima (INT). No rows give five
+ * empty Results and OK. The INT payloads keep an HBM shadow as every INT Result does. The
+ * operator runs on the calling device: a column held as row shards drops them and is split
+ * again on next use. A Column's min / max are not taken for key bounds (not every caller
+ * that builds a Column maintains them); the keys are read once more for them. ERROR and
+ * NULL (a "libmq:" line on stderr): no device, an argument that is neither a Column nor an
+ * INT Result, different lengths, 2^31 rows or more, a device failure. */
+Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
