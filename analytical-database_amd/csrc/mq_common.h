@@ -13,7 +13,9 @@ constexpr int kMaxDev = 64;
 
 struct DevState {
     bool ready;
-    int cus;                 // compute units (256 on MI355X)
+    int cus;                 // compute units the grids are sized for: hw_cus, or fewer
+                             // under mq_test_set_cu_limit
+    int hw_cus;              // compute units of the device (256 on MI355X)
     hipStream_t stream;      // library stream (mq_default_stream)
 };
 

@@ -1052,6 +1052,10 @@ int set_err(int code, const char* fmt, ...) {
 }
 
 DevState g_dev[kMaxDev];
+static int g_cu_limit = 0;  // mq_test_set_cu_limit: 0 = none
+
+// The CU count the grids are sized for: the device's, or the test limit when lower.
+static int limited_cus(int hw) { return g_cu_limit > 0 && g_cu_limit < hw ? g_cu_limit : hw; }
 
 int current_device(int* dev) {
     int d = -1;
@@ -1073,7 +1077,8 @@ int ensure_ready(DevState** out) {
         if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return set_err(MQ_ENODEV, "device %d is %s, libmq is built for gfx950 only", d,
                            prop.gcnArchName);
-        s.cus = prop.multiProcessorCount;
+        s.hw_cus = prop.multiProcessorCount;
+        s.cus = limited_cus(s.hw_cus);
         s.ready = true;
     }
     *out = &s;
@@ -1973,6 +1978,15 @@ void mq_scan_geometry(uint64_t n, uint32_t* blocks, uint64_t* rows_per_block) {
     geometry(s, n, scan_fn<kSum>(true), &g, &r);
     if (blocks) *blocks = g;
     if (rows_per_block) *rows_per_block = r;
+}
+
+// Test hook (mq_device.h): the grids are sized as on a device of at most `cus` CUs.
+int mq_test_set_cu_limit(int cus) {
+    if (cus < 0) return set_err(MQ_EINVAL, "mq_test_set_cu_limit: %d", cus);
+    g_cu_limit = cus;
+    for (int d = 0; d < kMaxDev; d++)
+        if (g_dev[d].ready) g_dev[d].cus = limited_cus(g_dev[d].hw_cus);
+    return MQ_OK;
 }
 
 int mq_gen_uniform(int32_t* d_out, uint64_t n, uint64_t seed, uint64_t modulus, void* stream) {

@@ -102,6 +102,17 @@ int mq_device_sync(void);
 size_t mq_scan_workspace_bytes(uint64_t n);
 /* The library's grid for a scan of n rows: blocks launched and rows per block. */
 void mq_scan_geometry(uint64_t n, uint32_t* blocks, uint64_t* rows_per_block);
+/* Test hook (no reference counterpart; as mq_shard_join_inject_failure in mq_query.h):
+ * size every grid as on a device of at most `cus` compute units, so that a column of a
+ * few million rows gives each block and wave the long row runs of a 1e9-row column.
+ * cus > 0: every device, initialised already or later, counts min(its CUs, cus);
+ * cus == 0: the hardware counts again (kept aside, no second device query);
+ * cus < 0: MQ_EINVAL. The count is only ever lowered: kernels that wait for
+ * lower-numbered blocks need the whole grid resident at once. The caller guarantees
+ * that no libmq work is in flight and that no other thread is inside libmq; workspace
+ * sizes that depend on the grid (mq_shared_select_workspace_bytes) are queried after
+ * the call. Off by default, and no environment variable sets it. */
+int mq_test_set_cu_limit(int cus);
 
 /* ---- synthetic data (bench/tests; SURVEY.md §8(c) generator) ---- */
 /* out[i] = (int32)(sm64(seed*0x100000001B3 + i) % modulus) */
