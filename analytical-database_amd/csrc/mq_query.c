@@ -1150,6 +1150,57 @@ Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Sta
     return out;
 }
 
+/* The first min(k, rows) entries of `values` in ascending or descending order, equal values
+ * in input order, and per entry its `positions` entry or row id (no reference counterpart;
+ * DESIGN.md §3.12): two INT Results. */
+Result** top_k(GeneralizedColumn* values, Result* positions, size_t k, bool descending, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const int32_t *dv = NULL, *dp = NULL;
+    size_t n = 0;
+    int bad = !values;
+    if (!bad) {
+        const int a = gcol_device(values, &dv, &n, ret_status);
+        if (a > 0) return NULL;
+        bad = a < 0;
+    }
+    if (!bad && positions) bad = positions->data_type != INT || (positions->num_tuples && !positions->payload);
+    if (bad || (positions && positions->num_tuples != n)) {
+        dml_fail(ret_status, "top_k",
+                 bad ? "values must be a Column or an INT Result, positions NULL or an INT Result"
+                     : "values and positions differ in length");
+        return NULL;
+    }
+    if (positions && result_device(positions, &dp, ret_status)) return NULL;
+    const size_t m = k < n ? k : n;
+    void* buf = NULL;
+    int rc = dev_alloc(&buf, m ? m * 2 * sizeof(int32_t) : 16);
+    int32_t* d_v = (int32_t*)buf;
+    int32_t* d_p = d_v + m;
+    if (!rc) rc = mq_topk(dv, dp, n, k, descending, MQ_TOPK_AUTO, 0, d_v, d_p, NULL, g_stream); /* synchronises */
+    if (rc) {
+        mq_pool_free(buf);
+        fail(ret_status, "top_k", rc);
+        return NULL;
+    }
+    Result** out = (Result**)calloc(2, sizeof(Result*));
+    out[0] = int_result_from_device(d_v, m, ret_status);
+    out[1] = int_result_from_device(d_p, m, ret_status);
+    mq_stream_sync(g_stream);
+    mq_pool_free(buf);
+    if (!out[0] || !out[1]) {
+        for (int j = 0; j < 2; j++)
+            if (out[j]) {
+                free(out[j]->payload);
+                free(out[j]);
+            }
+        free(out);
+        ret_status->code = ERROR;
+        return NULL;
+    }
+    ret_status->code = OK;
+    return out;
+}
+
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner
  * ascending — exactly a hash join that builds on the inner side (insertion
  * order = inner order) and probes with the outer side, outputs swapped. */

@@ -24,11 +24,18 @@ INT, LONG, FLOAT, DOUBLE = 0, 1, 2, 3
 OK, ERROR = 0, 1
 RESULT, COLUMN = 0, 1
 MQ_GROUP_AUTO, MQ_GROUP_DENSE, MQ_GROUP_SORT = 0, 1, 2
+MQ_TOPK_AUTO, MQ_TOPK_SELECT, MQ_TOPK_SORT = 0, 1, 2
+MQ_TOPK_SORT_DIV = 4
 
 
 class MqAgg(C.Structure):
     _fields_ = [("count", C.c_uint64), ("sum", C.c_int64), ("min", C.c_int32),
                 ("max", C.c_int32), ("_pad", C.c_uint64)]
+
+
+class MqTopkInfo(C.Structure):  # include/mq_device.h mq_topk_info
+    _fields_ = [("m", C.c_uint64), ("candidates", C.c_uint64), ("ties", C.c_uint64),
+                ("path", C.c_int32), ("levels", C.c_int32)]
 
 
 class ColumnIndex(C.Structure):
@@ -180,6 +187,9 @@ _SIGS = {
     "mq_group_plan": (_int, [_vp, _vp, _u64, _vp, _int, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_int), _vp]),
     "mq_group_write": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mq_group_free": (_int, [_vp]),
+    "mq_topk_default_cap": (_u64, []),
+    "mq_topk_auto_path": (_int, [_u64, _u64, _u64]),
+    "mq_topk": (_int, [_vp, _vp, _u64, _u64, _int, _int, _u64, _vp, _vp, C.POINTER(MqTopkInfo), _vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -223,6 +233,7 @@ _SIGS = {
     "nested_loop_join": (C.POINTER(_PR), [_PR, _PR, _PR, _PR, _PS]),
     "hash_join": (C.POINTER(_PR), [_PR, _PR, _PR, _PR, _PS]),
     "group_aggregate": (C.POINTER(_PR), [C.POINTER(GeneralizedColumn), C.POINTER(GeneralizedColumn), _PS]),
+    "top_k": (C.POINTER(_PR), [C.POINTER(GeneralizedColumn), _PR, _sz, C.c_bool, _PS]),
     "log_result": (None, [_PR]),
     "should_use_index": (C.c_bool, [C.POINTER(Column), _int, _int]),
     # load path (db_manager.h:254)

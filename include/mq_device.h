@@ -378,6 +378,48 @@ int mq_group_write(mq_group* g, int32_t* d_keys_out, uint64_t* d_count_out,
                    void* stream);
 int mq_group_free(mq_group* g);
 
+/* ---- top k: the k smallest or largest rows, in order ----
+ * n < 2^31 int32 values d_vals[i] with an optional int32 payload d_payload[i] (a positions
+ * vector, the pair select_result takes; NULL: the payload is the row id i). The output is
+ * m = min(k, n) pairs (value, payload): ascending, the m smallest values in ascending
+ * order; descending (descending != 0), the m largest in descending order; equal values by
+ * ascending input index i in both directions. That is the first m entries of a stable sort
+ * (numpy: argsort(v, kind="stable")[:m], of ~v for descending), so the result is unique and
+ * bitwise the same on every path and grid. The reference has no such operator.
+ * select: a radix select. Each value maps to a u32 key in output order (sign bit flipped,
+ *        complemented for descending). One streaming read counts the key's top 11 bits into
+ *        2048 bins; the bin that holds the m-th key is the boundary. While it holds more
+ *        than cand_cap rows the read is repeated over its rows alone for the next 11 bits,
+ *        then the last 10 (at most three reads: h_info->levels). One more read collects, in
+ *        input order, every row before the boundary prefix and the rows on it: all of them
+ *        when they fit cand_cap, else (the prefix is one value by then) only the first
+ *        m - (rows before) of them. The candidates, at most k + cand_cap, go through
+ *        mq_index_build and the first m are gathered. Workspace O(k + cand_cap + blocks).
+ * sort:  mq_index_build of the whole column (of ~v for descending), the first m gathered.
+ * MQ_TOPK_AUTO takes the sort path when min(k, n) + cand_cap > n / MQ_TOPK_SORT_DIV (so
+ * many candidates that selecting them saves nothing; mq_topk_auto_path answers the rule
+ * and needs no device), else the select path; MQ_TOPK_SELECT / MQ_TOPK_SORT force one for
+ * any k. cand_cap == 0 means mq_topk_default_cap().
+ * Synchronises (the host picks the boundary between the reads). Either output may be NULL;
+ * nothing is written at or past entry m. k == 0 or n == 0 gives m = 0 and MQ_OK.
+ * MQ_EINVAL, with nothing written: n >= 2^31, a NULL (n > 0) or misaligned (not 4-byte)
+ * d_vals or d_payload, a path that is none of the three. */
+enum { MQ_TOPK_AUTO = 0, MQ_TOPK_SELECT = 1, MQ_TOPK_SORT = 2 };
+enum { MQ_TOPK_SORT_DIV = 4 };
+typedef struct mq_topk_info {
+    uint64_t m;           /* entries written: min(k, n) */
+    uint64_t candidates;  /* entries handed to the final sort (sort path: n) */
+    uint64_t ties;        /* rows equal to the threshold value (entry m - 1) that were left out */
+    int32_t  path;        /* MQ_TOPK_SELECT or MQ_TOPK_SORT */
+    int32_t  levels;      /* histogram passes over the column (select path: 1..3; sort path: 0) */
+} mq_topk_info;
+uint64_t mq_topk_default_cap(void);   /* a constant; needs no device */
+int mq_topk_auto_path(uint64_t n, uint64_t k, uint64_t cand_cap /* 0: default */);
+int mq_topk(const int32_t* d_vals, const int32_t* d_payload /* may be NULL */, uint64_t n,
+            uint64_t k, int descending, int path, uint64_t cand_cap /* 0: default */,
+            int32_t* d_vals_out, int32_t* d_payload_out, mq_topk_info* h_info /* may be NULL */,
+            void* stream);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

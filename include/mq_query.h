@@ -282,6 +282,23 @@ void relational_insert(Db* db, Table* table, const int* rows, size_t nrows, Stat
  * INT Result, different lengths, 2^31 rows or more, a device failure. */
 Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Status* ret_status);
 
+/* ---- ORDER BY ... LIMIT k (not in the reference) ----
+ * top_k: the m = min(k, rows) smallest (descending: largest) entries of `values`, in order,
+ * with the rows they sit in (mq_topk in mq_device.h). `values` is a COLUMN
+ * or an INT RESULT, as sum and group_aggregate take them; `positions` is NULL or an INT
+ * Result of the same length, the (column, position) pair select_result takes. Returns a
+ * malloc'd array of two Result* with malloc'd payloads the caller frees (the hash_join
+ * contract): [0] the m values (INT), ascending, or descending when `descending`; [1] per
+ * value its entry of `positions`, or its row id when positions is NULL (INT). Equal values
+ * come in ascending input order in both directions, so the result is the first m entries of
+ * a stable sort. k == 0 or no rows give two empty Results and OK. Both payloads keep an HBM
+ * shadow as every INT Result does; resident copies and shadows of the inputs are used as
+ * the other operators use them. The operator runs on the calling device: a column held as
+ * row shards drops them and is split again on next use. ERROR and NULL (a "libmq:" line on
+ * stderr): no device, an argument of the wrong kind, different lengths, 2^31 rows or more,
+ * a device failure. */
+Result** top_k(GeneralizedColumn* values, Result* positions, size_t k, bool descending, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
