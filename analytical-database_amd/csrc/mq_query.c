@@ -1201,6 +1201,109 @@ Result** top_k(GeneralizedColumn* values, Result* positions, size_t k, bool desc
     return out;
 }
 
+/* The arguments select_where and aggregate_where share, resolved on the calling device:
+ * ncols columns (and `values`, when given) of one length *n, the bounds as mq_ranges, and
+ * the operator's workspace. 0, or nonzero with the failure reported. */
+static int where_args(const char* who, GeneralizedColumn** columns, int** lows, int** highs, int ncols,
+                      GeneralizedColumn* values, const int32_t** d_cols, mq_range* ranges, const int32_t** d_val,
+                      size_t* n, Status* st) {
+    if (ncols < 1 || ncols > MQ_WHERE_MAX_COLS) {
+        dml_fail(st, who, "ncols must be 1..8");
+        return -1;
+    }
+    int bad = !columns || !lows || !highs || (d_val && !values);
+    for (int c = 0; c < ncols && !bad; c++) bad = !columns[c];
+    int differ = 0;
+    for (int c = 0; c <= ncols && !bad; c++) {
+        if (c == ncols && !d_val) break;
+        size_t rows = 0;
+        const int a = gcol_device(c < ncols ? columns[c] : values, c < ncols ? &d_cols[c] : d_val, &rows, st);
+        if (a > 0) return -1;
+        bad = a < 0;
+        if (c == 0) *n = rows;
+        differ |= rows != *n;
+    }
+    if (bad || differ) {
+        dml_fail(st, who, bad ? "every column must be a Column or an INT Result" : "the columns differ in length");
+        return -1;
+    }
+    if (*n >= ((size_t)1 << 31)) {
+        dml_fail(st, who, "2^31 rows or more");
+        return -1;
+    }
+    for (int c = 0; c < ncols; c++)
+        ranges[c] = (mq_range){lows[c] != NULL, lows[c] ? *lows[c] : 0, highs[c] != NULL, highs[c] ? *highs[c] : 0};
+    if (ensure_ws(d_val ? 0 : *n, st)) return -1; /* the positions go to the staging buffer */
+    const int rc = grow(&g_ws, &g_ws_bytes, mq_where_workspace_bytes(*n));
+    if (rc) return fail(st, "workspace allocation", rc);
+    return 0;
+}
+
+/* WHERE c0 IN [..) AND c1 IN [..) ...: the positions (or `positions` entries) of the rows
+ * for which every range holds, ascending (no reference counterpart): what
+ * the chain select_column -> fetch_column -> select_result -> ... returns, in one operator. */
+Result* select_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols, Result* positions,
+                     Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t* dp = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0;
+    if (where_args("select_where", columns, lows, highs, ncols, NULL, d_cols, ranges, NULL, &n, ret_status)) return NULL;
+    if (positions) {
+        const int bad = positions->data_type != INT || (positions->num_tuples && !positions->payload);
+        if (bad || positions->num_tuples != n) {
+            dml_fail(ret_status, "select_where",
+                     bad ? "positions must be NULL or an INT Result" : "the columns and positions differ in length");
+            return NULL;
+        }
+        if (result_device(positions, &dp, ret_status)) return NULL;
+    }
+    int rc = mq_where_positions(d_cols, ranges, ncols, dp, n, (int32_t*)g_scratch, (uint64_t*)g_small, g_ws, g_ws_bytes,
+                                g_stream);
+    if (rc) {
+        fail(ret_status, "select_where", rc);
+        return NULL;
+    }
+    uint64_t k;
+    if (read_count(&k, ret_status)) return NULL;
+    return int_result_from_device(g_scratch, (size_t)k, ret_status);
+}
+
+/* count, sum, min and max of `values` over the rows for which every range holds (DESIGN.md
+ * §3.13): four one-tuple Results, count LONG, sum LONG, min INT, max INT. */
+Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn* values,
+                         Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t* dv = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0;
+    if (where_args("aggregate_where", columns, lows, highs, ncols, values, d_cols, ranges, &dv, &n, ret_status)) return NULL;
+    int rc = mq_where_agg(d_cols, ranges, ncols, dv, n, (mq_agg*)g_small, g_ws, g_ws_bytes, g_stream);
+    if (rc) {
+        fail(ret_status, "aggregate_where", rc);
+        return NULL;
+    }
+    mq_agg a;
+    if (read_agg(&a, ret_status)) return NULL;
+    long* cnt = (long*)malloc(sizeof(long));
+    long* sm = (long*)malloc(sizeof(long));
+    int* mn = (int*)malloc(sizeof(int));
+    int* mx = (int*)malloc(sizeof(int));
+    *cnt = (long)a.count;
+    *sm = (long)a.sum;
+    *mn = a.min;
+    *mx = a.max;
+    Result** out = (Result**)calloc(4, sizeof(Result*));
+    out[0] = new_result(LONG, 1, cnt);
+    out[1] = new_result(LONG, 1, sm);
+    out[2] = new_result(INT, 1, mn);
+    out[3] = new_result(INT, 1, mx);
+    ret_status->code = OK;
+    return out;
+}
+
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner
  * ascending — exactly a hash join that builds on the inner side (insertion
  * order = inner order) and probes with the outer side, outputs swapped. */

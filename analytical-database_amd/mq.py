@@ -26,6 +26,7 @@ RESULT, COLUMN = 0, 1
 MQ_GROUP_AUTO, MQ_GROUP_DENSE, MQ_GROUP_SORT = 0, 1, 2
 MQ_TOPK_AUTO, MQ_TOPK_SELECT, MQ_TOPK_SORT = 0, 1, 2
 MQ_TOPK_SORT_DIV = 4
+MQ_WHERE_MAX_COLS = 8
 
 
 class MqAgg(C.Structure):
@@ -36,6 +37,10 @@ class MqAgg(C.Structure):
 class MqTopkInfo(C.Structure):  # include/mq_device.h mq_topk_info
     _fields_ = [("m", C.c_uint64), ("candidates", C.c_uint64), ("ties", C.c_uint64),
                 ("path", C.c_int32), ("levels", C.c_int32)]
+
+
+class MqRange(C.Structure):  # include/mq_device.h mq_range
+    _fields_ = [("has_low", C.c_int32), ("low", C.c_int32), ("has_high", C.c_int32), ("high", C.c_int32)]
 
 
 class ColumnIndex(C.Structure):
@@ -190,6 +195,9 @@ _SIGS = {
     "mq_topk_default_cap": (_u64, []),
     "mq_topk_auto_path": (_int, [_u64, _u64, _u64]),
     "mq_topk": (_int, [_vp, _vp, _u64, _u64, _int, _int, _u64, _vp, _vp, C.POINTER(MqTopkInfo), _vp]),
+    "mq_where_workspace_bytes": (_sz, [_u64]),
+    "mq_where_positions": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "mq_where_agg": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -234,6 +242,10 @@ _SIGS = {
     "hash_join": (C.POINTER(_PR), [_PR, _PR, _PR, _PR, _PS]),
     "group_aggregate": (C.POINTER(_PR), [C.POINTER(GeneralizedColumn), C.POINTER(GeneralizedColumn), _PS]),
     "top_k": (C.POINTER(_PR), [C.POINTER(GeneralizedColumn), _PR, _sz, C.c_bool, _PS]),
+    "select_where": (_PR, [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                           C.POINTER(C.POINTER(_int)), _int, _PR, _PS]),
+    "aggregate_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                                         C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn), _PS]),
     "log_result": (None, [_PR]),
     "should_use_index": (C.c_bool, [C.POINTER(Column), _int, _int]),
     # load path (db_manager.h:254)

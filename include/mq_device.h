@@ -420,6 +420,46 @@ int mq_topk(const int32_t* d_vals, const int32_t* d_payload /* may be NULL */, u
             int32_t* d_vals_out, int32_t* d_payload_out, mq_topk_info* h_info /* may be NULL */,
             void* stream);
 
+/* ---- WHERE a IN [..) AND b IN [..) ...: a conjunctive range select ----
+ * ncols (1 .. MQ_WHERE_MAX_COLS) columns of n < 2^31 int32 rows and one range per column:
+ * row i matches when every range holds for it. A range is {has_low, low, has_high, high}
+ * and means low <= v < high with either bound optional, as everywhere in this header.
+ * d_cols is a HOST array of ncols device pointers, h_ranges a HOST array of ncols ranges;
+ * the same column may appear more than once. The reference has no such operator: its DSL
+ * spells a conjunction as the chain select -> fetch -> select_result -> fetch -> ...
+ * positions: in ascending i, d_payload ? d_payload[i] : i of every matching row into
+ *        d_pos_out (capacity n; nothing is written at or past entry K) and K into *d_count
+ *        (device). With ncols == 1 that is mq_select_positions bit for bit; for any ncols it
+ *        is what the chain returns.
+ * agg:   {count, int64 sum, min, max} of d_val[i] over the matching rows into *d_out
+ *        (device); with no match count and sum are 0, min INT32_MAX and max INT32_MIN, as
+ *        mq_select_agg leaves them. d_val may be one of the predicate columns.
+ * Every predicate column is streamed once at most; of column c + 1 only the 128-byte lines
+ * (32 rows) in which predicates 0..c left a row are requested, so the predicates are
+ * evaluated in the order given and libmq does not reorder them: the answer does not depend
+ * on the order, the traffic does. PUT THE MOST SELECTIVE PREDICATE FIRST. A range with
+ * neither bound matches every row and its column is not read; a range that no int32 can
+ * satisfy gives K = 0, or the empty aggregate, without reading any column (the outputs are
+ * still written on `stream`). Integer operations only: the result is bitwise the same
+ * whatever the grid, the order of the predicates or the alignment of the pointers. Columns
+ * that are not all 16-byte aligned are read with dword loads.
+ * Both calls are asynchronous on `stream`. d_ws: mq_where_workspace_bytes(n) bytes, 16-byte
+ * aligned (positions: one bit per row, a count per 256 rows and the scan's scratch behind
+ * the per-block partials). n == 0 gives K = 0, or the empty aggregate, and MQ_OK.
+ * MQ_EINVAL, with nothing written: ncols outside 1..8, n >= 2^31, a NULL h_ranges or
+ * d_cols, a NULL or not 4-byte aligned column, payload, value column or output with n > 0,
+ * a NULL output count or aggregate, a NULL, short or misaligned workspace. */
+enum { MQ_WHERE_MAX_COLS = 8 };
+typedef struct mq_range { int32_t has_low, low, has_high, high; } mq_range;   /* 16 bytes */
+size_t mq_where_workspace_bytes(uint64_t n);          /* needs no device */
+int mq_where_positions(const int32_t* const* d_cols /* host array of ncols device pointers */,
+                       const mq_range* h_ranges, int ncols, const int32_t* d_payload /* may be NULL */,
+                       uint64_t n, int32_t* d_pos_out /* capacity n */, uint64_t* d_count /* device */,
+                       void* d_ws, size_t ws_bytes, void* stream);
+int mq_where_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols,
+                 const int32_t* d_val, uint64_t n, mq_agg* d_out /* device */,
+                 void* d_ws, size_t ws_bytes, void* stream);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

@@ -299,6 +299,33 @@ Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Sta
  * a device failure. */
 Result** top_k(GeneralizedColumn* values, Result* positions, size_t k, bool descending, Status* ret_status);
 
+/* ---- WHERE a IN [..) AND b IN [..) ... (not in the reference) ----
+ * A conjunction of 1 to 8 range predicates in one operator (DESIGN.md §3.13;
+ * mq_where_positions / mq_where_agg in mq_device.h). The reference's DSL spells it as the
+ * chain select_column -> fetch_column -> select_result -> fetch_column -> ...; these return
+ * what that chain returns without materialising its intermediates. Each entry of `columns`,
+ * and `values`, is a COLUMN or an INT RESULT, as sum and top_k take them; all must be equally
+ * long. lows[c] and highs[c] are NULL or point to the bound of columns[c], as select_column's
+ * `int* low, int* high`: row i matches when low <= columns[c][i] < high holds for every c.
+ * The predicates are evaluated in the order given: put the most selective one first (the
+ * answer does not depend on the order, the memory traffic does).
+ * select_where: a malloc'd INT Result of the K matching row positions in ascending order,
+ *   or, with `positions` (an INT Result as long as the columns), of its entries at those
+ *   rows. The payload is obtained, downloaded and shadowed in HBM as select_result's is.
+ * aggregate_where: a malloc'd array of four one-tuple Results with malloc'd payloads the
+ *   caller frees: [0] the count of matching rows (LONG), [1] the sum of `values` over them
+ *   (LONG), [2] their min (INT; INT32_MAX without a match), [3] their max (INT; INT32_MIN).
+ *   `values` may be one of the predicate columns.
+ * Resident copies and shadows of the inputs are used as the other operators use them. The
+ * operator runs on the calling device: a column held as row shards drops them and is split
+ * again on next use. ERROR and NULL (a "libmq:" line on stderr): no device, ncols outside
+ * 1..8, an argument of the wrong kind, different lengths, 2^31 rows or more, a device
+ * failure. */
+Result* select_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
+                     Result* positions /* NULL or INT, same length */, Status* ret_status);
+Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
+                         GeneralizedColumn* values, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
