@@ -2238,17 +2238,19 @@ int mq_index_select(const int32_t* d_values, const uint64_t* d_positions, uint64
     }
     if (!d_values || !d_positions || !d_pos_out)
         return set_err(MQ_EINVAL, "mq_index_select: NULL pointer");
-    // run = {left, k}: 16 bytes of scratch kept with the device state.
-    static thread_local long long* run_buf[kMaxDev];
-    int d;
-    if ((rc = current_device(&d))) return rc;
-    if (!run_buf[d]) HIPCHK(hipMalloc(&run_buf[d], 2 * sizeof(long long)));
-    hipLaunchKernelGGL(k_index_bounds, dim3(1), dim3(64), 0, st, d_values, n, low, high, run_buf[d],
+    // run = {left, k}: 16 bytes of scratch of this call alone, from the stream-ordered pool
+    // (calls queued on different streams must not share it), given back behind k_index_copy.
+    long long* run = static_cast<long long*>(pool_alloc(2 * sizeof(long long)));
+    if (!run) return set_err(MQ_ENOMEM, "mq_index_select: allocation failed");
+    hipLaunchKernelGGL(k_index_bounds, dim3(1), dim3(64), 0, st, d_values, n, low, high, run,
                        reinterpret_cast<unsigned long long*>(d_count));
-    LAUNCHCHK("k_index_bounds");
-    hipLaunchKernelGGL(k_index_copy, dim3(stream_grid(s, n)), dim3(kTPB), 0, st, d_positions,
-                       run_buf[d], d_pos_out);
-    LAUNCHCHK("k_index_copy");
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_index_copy, dim3(stream_grid(s, n)), dim3(kTPB), 0, st, d_positions, run, d_pos_out);
+        e = hipGetLastError();
+    }
+    pool_free_on(run, st);
+    if (e != hipSuccess) return set_err(MQ_EHIP, "mq_index_select: launch failed: %s", hipGetErrorString(e));
     return MQ_OK;
 }
 

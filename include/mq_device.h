@@ -227,7 +227,12 @@ int mq_select_positions_download(const int32_t* d_col, uint64_t n, int has_low, 
 /* ---- S6 select_column_sorted_index (query.c:143-198) ----
  * d_values: n int32 sorted ascending; d_positions: n size_t row ids. Restates the
  * reference's binary_search + run adjustment exactly (including its low == high
- * quirk), writes the run's positions (as int32) to d_pos_out, K to *d_count. */
+ * quirk), writes the run's positions (as int32) to d_pos_out, K to *d_count.
+ * A bound below d_values[0], where the reference reads out of bounds, is defined: such a
+ * low starts the run at row 0, such a high selects nothing. Calls queued on different
+ * streams are independent (each takes its own scratch from the stream-ordered pool).
+ * k_index_bounds walks a run of `low` / `high` on a single lane, one dependent load per
+ * step. Nobody has measured what a long run costs. */
 int mq_index_select(const int32_t* d_values, const uint64_t* d_positions, uint64_t n, int32_t low,
                     int32_t high, int32_t* d_pos_out, uint64_t* d_count, void* stream);
 

@@ -869,3 +869,43 @@ void rc_histogram(const int32_t* col, size_t n, int32_t mn, int32_t bin_size, ui
         counts[(b >= 0 && b < 100) ? b : 100]++;
     }
 }
+
+/* binary_search (query.c:143-160) on signed indices: the row of some value equal to
+ * target, else the last row whose value is below it, -1 where there is none (the
+ * reference's unsigned `right` wraps there and it reads out of bounds). */
+static int64_t idx_search(const int32_t* values, int64_t n, int32_t target) {
+    int64_t lo = 0, hi = n - 1;
+    while (lo <= hi) {
+        const int64_t mid = (lo + hi) / 2;
+        if (values[mid] == target) return mid;
+        if (target < values[mid]) hi = mid - 1;
+        else lo = mid + 1;
+    }
+    return hi;
+}
+
+/* select_column_sorted_index (query.c:165-198) over a sorted index (values ascending,
+ * positions the row each came from): the rows from the first value >= low up to the
+ * row before the first value == high, or the last value below high. Two quirks are the
+ * reference's own and kept: the walk down a run of `high` stops at `left`, so
+ * low == high present in the column selects one row, and so does a `high` that is
+ * present with nothing in [low, high) before it. Two cases the reference leaves
+ * undefined are defined as libmq's k_index_bounds defines them: low below values[0]
+ * starts at row 0, high below values[0] selects nothing. Positions are truncated to
+ * int32 as the reference's int result array truncates them. Returns K. */
+size_t rc_index_select(const int32_t* values, const uint64_t* positions, size_t n, int32_t low, int32_t high,
+                       int32_t* pos_out) {
+    if (n == 0) return 0;
+    int64_t left = idx_search(values, (int64_t)n, low);
+    int64_t right = idx_search(values, (int64_t)n, high);
+    if (left < 0) {
+        left = 0;
+    } else {
+        while (left > 0 && values[left] >= low) left--;
+        if (values[left] != low) left++;
+    }
+    while (right > left && values[right] == high) right--;
+    size_t k = 0;
+    for (int64_t row = left; row <= right; row++) pos_out[k++] = (int32_t)positions[row];
+    return k;
+}

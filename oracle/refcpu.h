@@ -94,6 +94,13 @@ void rc_histogram(const int32_t* col, size_t n, int32_t mn, int32_t bin_size, ui
 size_t rc_load_csv(const char* text, size_t n, int ncols, int32_t** cols, size_t cap,
                    int32_t* minmax);
 
+/* ---- sorted-index select (query.c:143-198) over the index's (values, positions) ----
+ * pos_out (capacity n) receives (int32_t)positions[row] of the selected run; returns K.
+ * Signed indices: a bound below values[0] searches to -1, which for low means "from
+ * row 0" and for high an empty run (the reference reads out of bounds there). */
+size_t rc_index_select(const int32_t* values, const uint64_t* positions, size_t n, int32_t low, int32_t high,
+                       int32_t* pos_out);
+
 #ifdef __cplusplus
 }
 #endif

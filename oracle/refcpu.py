@@ -68,6 +68,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "rc_index_build": (None, [_vp, _sz, _vp, _vp]),
         "rc_index_build_lomuto": (None, [_vp, _sz, _vp, _vp]),
         "rc_histogram": (None, [_vp, _sz, _i32, _i32, _vp]),
+        "rc_index_select": (_sz, [_vp, _vp, _sz, _i32, _i32, _vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -275,6 +276,18 @@ def index_build_lomuto(col: np.ndarray):
     p = np.empty(max(len(col), 1), dtype=np.uint64)
     lib().rc_index_build_lomuto(_a(col), len(col), _a(v), _a(p))
     return v[:len(col)].copy(), p[:len(col)].copy()
+
+
+def index_select(values: np.ndarray, positions: np.ndarray, low: int, high: int) -> np.ndarray:
+    """select_column_sorted_index (query.c:143-198) over a sorted index: the selected
+    run's positions as int32 (uint64 positions truncated, as the reference's int array
+    does)."""
+    values = np.ascontiguousarray(values, dtype=np.int32)
+    positions = np.ascontiguousarray(positions, dtype=np.uint64)
+    assert len(values) == len(positions)
+    out = np.empty(max(len(values), 1), dtype=np.int32)
+    k = lib().rc_index_select(_a(values), _a(positions), len(values), int(low), int(high), _a(out))
+    return out[:k].copy()
 
 
 def histogram(col: np.ndarray, mn: int, bin_size: int) -> np.ndarray:

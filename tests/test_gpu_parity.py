@@ -559,8 +559,10 @@ def test_query_api_sorted_index_vs_reference(lib, refcpu):
     col = make_column(d)
     col.has_index = True
     col.index = C.pointer(ix)
-    # low >= values[0] (the reference reads out of bounds below that)
-    for lo, hi in ((0, 10), (3, 3), (7, 2), (100, 499), (250, 251), (0, 1000), (499, 600)):
+    # low >= values[0] and high >= values[0] (the reference's unsigned binary_search reads out
+    # of bounds for either bound below that)
+    for lo, hi in ((0, 10), (3, 3), (7, 2), (100, 499), (250, 251), (0, 1000), (499, 600), (499, 499),
+                   (501, 600)):
         assert np.array_equal(ref.select_column(col, lo, hi), mine.select_column(col, lo, hi)), \
             (lo, hi)
 

@@ -6,8 +6,11 @@ main loop, k_select_stage's ring + spill and its switch to bitmap mode, the long
 wave-chunks of shared select and of k_group_dense then run only in the 1e9-row tests,
 which check properties on uniform data. mq_test_set_cu_limit (mq_device.h) lowers the CU
 count the geometry uses; with 1, 2 or 7 CUs a column of 0.3-4 M rows gives each block
-what a 1e9-row column gives it on the whole device. Expected values come from numpy, the
-refcpu oracle and groupcases.py; each test asserts first that its regime is reached.
+what a 1e9-row column gives it on the whole device. The grid-stride operators (fetch,
+add / sub, gather, histogram, hashset lookup) take a second step of their loops only past
+524 288 work items on the whole device; under a limit a few thousand are enough. Expected
+values come from numpy, the refcpu oracle and groupcases.py; each test asserts first that
+its regime is reached.
 """
 import ctypes as C
 
@@ -390,7 +393,227 @@ def test_group_dense_long_chunks(lib, limit, keyset):
 
 
 # ---------------------------------------------------------------------------
-# e. the hook itself
+# e. the grid-stride operators: fetch, add / sub, gather, histogram, hashset lookup
+#
+# stream_grid launches min(ceil(work / 256), 8 x CUs) blocks of 256 threads, so under a
+# limit the grid has S = lanes(cus) lanes and a lane's loop repeats once the work passes S
+# items: on the whole device that takes 524 288.
+# ---------------------------------------------------------------------------
+PAD = 8  # sentinel words kept after every output
+
+
+def lanes(cus):
+    return 8 * cus * 256
+
+
+def _refill(lib, d):
+    mq.check(lib.mq_memset(d.ptr, 0x5A, d.nbytes, None), "mq_memset")
+
+
+def _check_out(out, off, want, tag):
+    """out holds `want` from word `off` on and 0x5A everywhere else."""
+    got = out.get(np.int32, off + len(want) + PAD)
+    assert np.array_equal(got[off:off + len(want)], want), tag
+    assert np.all(got[:off] == SENT) and np.all(got[off + len(want):] == SENT), tag + ("wrote outside the output",)
+
+
+_fetch_cache = {}
+
+
+def _fetch_data():
+    """A 500 000-row full-range column, aligned and +4 B, and the most positions any case
+    uses (random with repeats), made once."""
+    if not _fetch_cache:
+        rng = np.random.default_rng(41)
+        col = rng.integers(I32MIN, I32MAX, 500_000, dtype=np.int64, endpoint=True).astype(np.int32)
+        col[:2], col[-2:] = (I32MIN, I32MAX), (I32MAX, I32MIN)
+        kmax = 4 * (11 * lanes(max(LIMITS)) + 5) + 3
+        pos = rng.integers(0, len(col), kmax).astype(np.int32)
+        pos[::1001], pos[7::1001] = 0, len(col) - 1
+        _fetch_cache.update(col=col, pos=pos, cols=[Dev.of(col), Dev.of(col, offset_elems=1)],
+                            poss=[Dev.of(pos), Dev.of(pos, offset_elems=1)], out=Dev(4 * (kmax + 2 * PAD)))
+    return _fetch_cache
+
+
+@pytest.mark.parametrize("cus", LIMITS)
+def test_fetch_unrolled_steps(lib, limit, cus):
+    """k_fetch where its unrolled step (4 groups of 4 positions a lane), the one-group loop
+    and the tail hand over to each other: k4 groups at and around 3S, 4S, between and far
+    past, k = 4 k4 + {0, 3}; all pointers aligned (k_fetch<true>), the positions or the
+    output alone 4 B off (k_fetch<false>), the column 4 B off; positions descending once."""
+    limit(cus)
+    S = lanes(cus)
+    groups = [3 * S, 3 * S + 1, 4 * S, 4 * S + 1, 5 * S + S // 2, 11 * S + 5]
+    # at 3S groups no lane takes the unrolled step and every lane the one-group loop 3 times;
+    # from 3S + 1 on the unrolled step runs, at 11S + 5 twice and then the one-group loop
+    assert min(groups) >= 3 * S and max(groups) > 2 * 4 * S + 3 * S
+    c = _fetch_data()
+    col, pos, out = c["col"], c["pos"], c["out"]
+    # (column, positions, output) offsets in dwords
+    layouts = {"aligned": (0, 0, 0), "pos +4 B": (0, 1, 0), "out +4 B": (0, 0, 1), "col +4 B": (1, 0, 0)}
+    for k4 in groups:
+        for r in (0, 3):
+            k = 4 * k4 + r
+            want = col[pos[:k]]
+            for name, (co, po, oo) in layouts.items():
+                _refill(lib, out)
+                mq.check(lib.mq_fetch(c["cols"][co].ptr, c["poss"][po].ptr, k, out.ptr + 4 * oo, None), "mq_fetch")
+                _check_out(out, oo, want, (cus, k4, r, name))
+    k = 4 * groups[-1] + 3
+    desc = np.sort(pos[:k])[::-1].copy()
+    dd = Dev.of(desc)
+    _refill(lib, out)
+    mq.check(lib.mq_fetch(c["cols"][0].ptr, dd.ptr, k, out.ptr, None), "mq_fetch")
+    _check_out(out, 0, col[desc], (cus, "descending"))
+
+
+def test_fetch_at_row_base(lib, limit):
+    """mq_fetch_at on a 50 000-row shard whose rows start at 1 000 003: out = shard[pos -
+    row_base], past the unrolled step; row base 0 is mq_fetch; a negative one is refused."""
+    limit(1)
+    S = lanes(1)
+    k = 4 * (4 * S + 1) + 3
+    assert k // 4 > 3 * S
+    rng = np.random.default_rng(43)
+    shard = rng.integers(I32MIN, I32MAX, 50_000, dtype=np.int64, endpoint=True).astype(np.int32)
+    local = rng.integers(0, len(shard), k).astype(np.int32)
+    local[:4] = (0, len(shard) - 1, 0, len(shard) - 1)
+    ds, out = Dev.of(shard), Dev(4 * (k + 2 * PAD))
+    for base in (ROW_BASE, 0):
+        dp = Dev.of(local + np.int32(base))
+        _refill(lib, out)
+        mq.check(lib.mq_fetch_at(ds.ptr, base, dp.ptr, k, out.ptr, None), "mq_fetch_at")
+        _check_out(out, 0, shard[local], ("fetch_at", base))
+        if base == 0:
+            at = out.get(np.int32, k + PAD)
+            _refill(lib, out)
+            mq.check(lib.mq_fetch(ds.ptr, dp.ptr, k, out.ptr, None), "mq_fetch")
+            assert np.array_equal(out.get(np.int32, k + PAD), at)
+    _refill(lib, out)
+    assert lib.mq_fetch_at(ds.ptr, -1, dp.ptr, k, out.ptr, None) == mq.MQ_EINVAL
+    assert np.all(out.get(np.int32, k + PAD) == SENT)
+
+
+ADDSUB_PAIRS = [(I32MIN, I32MIN), (I32MAX, I32MAX), (I32MIN, I32MAX), (I32MAX, I32MIN), (-1, I32MIN)]
+_addsub_cache = {}
+
+
+def _addsub_data(refcpu, n, S):
+    """Full-range a and b of n rows with the wrap-around pairs planted in every sweep of
+    4 S rows (from its row 6 on, across two groups of 4), and the oracle's a + b and a - b."""
+    if n not in _addsub_cache:
+        rng = np.random.default_rng(n)
+        a = rng.integers(I32MIN, I32MAX, n, dtype=np.int64, endpoint=True).astype(np.int32)
+        b = rng.integers(I32MIN, I32MAX, n, dtype=np.int64, endpoint=True).astype(np.int32)
+        planted = 0
+        for at in range(6, n - len(ADDSUB_PAIRS) + 1, 4 * S):
+            for j, (x, y) in enumerate(ADDSUB_PAIRS):
+                a[at + j], b[at + j] = x, y
+            planted += 1
+        assert planted >= n // (4 * S)
+        _addsub_cache[n] = (a, b, refcpu.add(a, b), refcpu.sub(a, b))
+    return _addsub_cache[n]
+
+
+@pytest.mark.parametrize("layout", ["aligned", "a +4 B", "b +4 B", "out +4 B"])
+def test_add_sub_sweeps_and_layouts(lib, refcpu, limit, layout):
+    """mq_add and mq_sub over one to six sweeps of the grid with all pointers 16-byte aligned
+    (k_addsub<*, true>) and with a, b or the output alone 4 B off (k_addsub<*, false>, the
+    scalar instance), two's-complement wrap at the INT32 extremes in every sweep."""
+    limit(1)
+    S = lanes(1)
+    sizes = [4 * S, 4 * S + 1, 4 * (2 * S + 1) + 3, 4 * (5 * S + 77) + 2]
+    assert min(sizes) // 4 >= S and max(sizes) // 4 > 5 * S  # the grid is full; up to 6 sweeps
+    ao, bo, oo = {"aligned": (0, 0, 0), "a +4 B": (1, 0, 0), "b +4 B": (0, 1, 0), "out +4 B": (0, 0, 1)}[layout]
+    for n in sizes:
+        a, b, want_add, want_sub = _addsub_data(refcpu, n, S)
+        assert np.array_equal(want_add, (a.astype(np.int64) + b).astype(np.int32))  # the oracle wraps
+        da, db, out = Dev.of(a, offset_elems=ao), Dev.of(b, offset_elems=bo), Dev(4 * (n + 2 * PAD))
+        for fn, want in ((lib.mq_add, want_add), (lib.mq_sub, want_sub)):
+            _refill(lib, out)
+            mq.check(fn(da.ptr, db.ptr, n, out.ptr + 4 * oo, None), "mq_add/mq_sub")
+            _check_out(out, oo, want, (layout, n, "add" if fn is lib.mq_add else "sub"))
+
+
+@pytest.mark.parametrize("cus", [1, 2])
+def test_gather_u64_full_steps(lib, limit, cus):
+    """k_gather_u64 around one full grid step of G = lanes x 8 rows and past three: its
+    unguarded main loop repeats and the guarded last step follows it."""
+    limit(cus)
+    G = lanes(cus) * 8
+    assert G == 8 * cus * 2048
+    sizes = [G - 1, G, G + 1, 3 * G + 2049]
+    assert max(sizes) > 3 * G + 7 * 256  # some lanes take a fourth full step
+    rng = np.random.default_rng(47 + cus)
+    col = rng.integers(I32MIN, I32MAX, 300_000, dtype=np.int64, endpoint=True).astype(np.int32)
+    pos = rng.integers(0, len(col), max(sizes)).astype(np.uint64)
+    pos[:2], pos[-2:] = (0, len(col) - 1), (len(col) - 1, 0)
+    dc, dp, out = Dev.of(col), Dev.of(pos), Dev(4 * (max(sizes) + 2 * PAD))
+    for n in sizes:
+        _refill(lib, out)
+        mq.check(lib.mq_gather_u64(dc.ptr, dp.ptr, n, out.ptr, None), "mq_gather_u64")
+        _check_out(out, 0, col[pos[:n].astype(np.int64)], (cus, n))
+
+
+def test_histogram_many_sweeps(lib, refcpu, limit):
+    """k_histogram where every lane counts 146 rows: the (min, bin) pairs of
+    test_gather_and_histogram_vs_oracle, and a full-range column binned from INT32_MIN."""
+    limit(1)
+    n = 300_000
+    assert n > 100 * lanes(1)
+    rng = np.random.default_rng(9)
+    col = rng.integers(-10**6, 10**6, n).astype(np.int32)
+    wide = _wide(n, 53)
+    cases = [(col, int(col.min()), (int(col.max()) - int(col.min())) // 99), (col, 0, 7), (col, -10, -3),
+             (wide, I32MIN, 43_383_508)]
+    h = Dev(8 * (101 + 2))
+    dcs = {id(col): Dev.of(col), id(wide): Dev.of(wide)}
+    for c, mn, bs in cases:
+        assert bs not in (0, -1)  # INT32_MIN / -1 traps in the oracle
+        _refill(lib, h)
+        mq.check(lib.mq_histogram(dcs[id(c)].ptr, n, mn, bs, h.ptr, None), "mq_histogram")
+        got = h.get(np.uint64, 103)
+        want = refcpu.histogram(c, mn, bs)
+        assert int(want.sum()) == n
+        assert np.array_equal(got[:101], want), (mn, bs)
+        assert np.all(got[101:] == np.uint64(0x5A5A5A5A5A5A5A5A)), (mn, bs, "wrote past the counts")
+
+
+def test_hashset_lookup_many_sweeps(lib, refcpu, limit):
+    """k_hashset_lookup on 300 000 probes (146 a lane): members, keys that share a member's
+    home slot, non-members, 0 and negatives, on the tables of hashsetcases.py that are at
+    most half full, against the restatement's lookup."""
+    import hashsetcases as hc
+    limit(1)
+    nprobe = 300_000
+    assert nprobe > 100 * lanes(1)
+    tables = {name: (size, keys) for name, (size, keys) in hc.LISTS.items()
+              if len({int(k) for k in keys} - {0}) * 2 <= size}
+    assert len(tables) >= 3, sorted(tables)
+    found = Dev(nprobe + 16)
+    for name, (size, keys) in sorted(tables.items()):
+        t = hc.expected_table(refcpu, size, keys)
+        rng = np.random.default_rng(size)
+        members = np.array([k for k in keys if k != 0], dtype=np.int64)
+        pool = np.concatenate([members, members + size, members - size, members + 7 * size, -members,
+                               rng.integers(I32MIN, I32MAX, 4000, endpoint=True), np.arange(-50, 50),
+                               [0, I32MIN, I32MAX, I32MIN + 1, size, -size]])
+        pool = pool[(pool >= I32MIN) & (pool <= I32MAX)].astype(np.int32)
+        probes = pool[rng.integers(0, len(pool), nprobe)]
+        probes[:len(pool)] = pool
+        answer = {int(k): refcpu.hashset_lookup(t, int(k)) for k in np.unique(probes)}
+        want = np.array([answer[int(k)] for k in probes.tolist()], dtype=np.uint8)
+        assert 0 < want.sum() < nprobe and all(answer[int(k)] for k in members)
+        dt, dp = Dev.of(t), Dev.of(probes)
+        _refill(lib, found)
+        mq.check(lib.mq_hashset_lookup(dt.ptr, size, dp.ptr, nprobe, found.ptr, None), "mq_hashset_lookup")
+        got = found.get(np.uint8, nprobe + 16)
+        assert np.array_equal(got[:nprobe], want), name
+        assert np.all(got[nprobe:] == 0x5A), (name, "wrote past the answers")
+
+
+# ---------------------------------------------------------------------------
+# f. the hook itself
 # ---------------------------------------------------------------------------
 def test_cu_limit_restores_and_never_raises(lib, limit, hardware):
     """After mq_test_set_cu_limit(0) mq_scan_geometry answers as before any limit; a

@@ -2,8 +2,13 @@
 rc_histogram, composed as build_index in tests/indexcases.py model()) against the
 reference's own build_index (tests/golden/index_goldens.json, from
 oracle/_ref/libdbm.so) and its own quicksort symbol: exact, equal values included.
+And the sorted-index select restatement (rc_index_select) against a closed form on
+every small case and against the reference's own select_column_sorted_index.
 CPU only.
 """
+import bisect
+import ctypes as C
+import itertools
 import json
 import os
 
@@ -112,3 +117,106 @@ def test_lomuto_restatement_2e22_vs_reference_quicksort(refcpu, case):
     if case["seed"] == 42 and refload.have():
         rv, rp = refload.quicksort(col)
         assert np.array_equal(v, rv) and np.array_equal(p, rp)
+
+
+# ---------------------------------------------------------------------------
+# sorted-index select: rc_index_select
+# ---------------------------------------------------------------------------
+I32MAX = 2 ** 31 - 1
+
+
+def closed_form_run(values, low, high):
+    """(first row, K) of the sorted-index select over the ascending list `values`.
+    With lb(x) the first row whose value is >= x: the run is [lb(low), lb(high) - 1],
+    except that a `high` present in the column with low <= high never leaves the run
+    empty (the reference's walk down the run of `high` stops at `left`): one row then."""
+    left = bisect.bisect_left(values, low)
+    right = bisect.bisect_left(values, high) - 1
+    if low <= high and right + 1 < len(values) and values[right + 1] == high:
+        right = max(right, left)
+    return left, max(0, right - left + 1)
+
+
+def test_index_select_restatement_vs_closed_form(refcpu):
+    """Every non-decreasing column of 1..7 rows over {0..4} and every low, high in
+    -1..5, bounds below the first value (the two defined extensions) included."""
+    ncases = 0
+    for n in range(1, 8):
+        positions = (np.arange(n, dtype=np.uint64) * 7 + 3)[::-1].copy()
+        want_pos = positions.astype(np.int32)
+        for vals in itertools.combinations_with_replacement(range(5), n):
+            v = np.array(vals, dtype=np.int32)
+            for low in range(-1, 6):
+                for high in range(-1, 6):
+                    left, k = closed_form_run(vals, low, high)
+                    got = refcpu.index_select(v, positions, low, high)
+                    assert np.array_equal(got, want_pos[left:left + k]), (vals, low, high)
+                    ncases += 1
+    assert ncases == 38_759
+
+
+def _ref_select_columns():
+    """name, unsorted column: distinct values, short runs (both with gaps, so a value's
+    neighbours are absent), all-equal, and values up to INT32_MAX, at 1, 2, 65 and 4097 rows."""
+    rng = np.random.default_rng(21)
+    for n in (1, 2, 65, 4097):
+        yield f"distinct_{n}", (rng.permutation(n) * 3 + 10).astype(np.int32)
+        yield f"runs_{n}", (rng.integers(0, n // 3 + 1, n) * 3 - 6).astype(np.int32)
+        yield f"equal_{n}", np.full(n, 7, dtype=np.int32)
+        top = rng.integers(I32MAX - 8, I32MAX, n, endpoint=True).astype(np.int32)
+        top[0] = I32MAX
+        yield f"int32max_{n}", top
+
+
+def _ref_select_bounds(values):
+    """(low, high) pairs the reference defines: both >= values[0] (below that its unsigned
+    binary_search reads out of bounds). The first, a middle and the last value, each -1,
+    +0 and +1, a bound well above the last value and INT32_MAX, in every pair: low > high,
+    low == high, and high present with nothing in [low, high) are among them."""
+    u = np.unique(values)
+    picks = {int(u[0]), int(u[len(u) // 2]), int(u[-1])}
+    cand = {p + d for p in picks for d in (-1, 0, 1)} | {int(u[-1]) + 1000, I32MAX}
+    cand = sorted(c for c in cand if int(values[0]) <= c <= I32MAX)
+    for low in cand:
+        for high in cand:
+            assert low >= values[0] and high >= values[0], (low, high)  # never call the reference below
+            yield low, high
+
+
+def test_index_select_restatement_vs_reference(refcpu):
+    """rc_index_select against the reference's own select_column_sorted_index
+    (oracle/_ref/libref.so), the indexed column built as the drop-in test builds it."""
+    if not refcpu.have_reference():
+        pytest.skip("oracle/_ref/libref.so not built (no reference sources)")
+    from refapi import make_column, mq, take
+    ref = refcpu.reference()
+    seen = {"low == high present": 0, "high present, [low, high) empty": 0, "low > high": 0,
+            "both above the last value": 0, "INT32_MAX bound": 0, "INT32_MAX value": 0}
+    for name, d in _ref_select_columns():
+        order = np.argsort(d, kind="stable")
+        values = np.ascontiguousarray(d[order])
+        positions = np.ascontiguousarray(order.astype(np.uint64))
+        ix = mq.ColumnIndex()
+        ix.values = values.ctypes.data_as(C.POINTER(C.c_int))
+        ix.positions = positions.ctypes.data_as(C.POINTER(C.c_size_t))
+        col = make_column(d)
+        col.has_index = True
+        col.index = C.pointer(ix)
+        vlist = values.tolist()
+        for low, high in _ref_select_bounds(values):
+            st = mq.Status(0, None)
+            want = take(ref.select_column_sorted_index(C.byref(col), low, high, C.byref(st)))
+            assert st.code == mq.OK
+            got = refcpu.index_select(values, positions, low, high)
+            assert np.array_equal(got, want), (name, low, high)
+            left, k = closed_form_run(vlist, low, high)
+            assert np.array_equal(got, positions[left:left + k].astype(np.int32)), (name, low, high)
+            present = bisect.bisect_left(vlist, high) < bisect.bisect_right(vlist, high)
+            seen["low == high present"] += low == high and present
+            seen["high present, [low, high) empty"] += (low < high and present and
+                                                      bisect.bisect_left(vlist, low) == bisect.bisect_left(vlist, high))
+            seen["low > high"] += low > high
+            seen["both above the last value"] += low > vlist[-1] and high > vlist[-1]
+            seen["INT32_MAX bound"] += I32MAX in (low, high)
+            seen["INT32_MAX value"] += vlist[-1] == I32MAX
+    assert all(seen.values()), seen
