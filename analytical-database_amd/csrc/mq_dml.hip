@@ -93,6 +93,15 @@ Layout layout(uint64_t n) {
     return l;
 }
 
+// The fixed grids of the chunked passes: the word prefix over words + 1 entries
+// (k_dml_word_sums, k_dml_word_prefix) and the index pass over n entries
+// (k_dml_index_count, k_dml_index_write).
+void prefix_chunks(uint64_t words, uint32_t* blocks, uint64_t* chunk) {
+    chunks(words + 1, kTPB, kRankBlocks, blocks, chunk);
+}
+
+void index_chunks(uint64_t n, uint32_t* blocks, uint64_t* chunk) { chunks(n, kIdxStep, kIdxBlocks, blocks, chunk); }
+
 // The plan last made by this thread: the apply steps take their sizes from it.
 struct Plan {
     const void* ws;
@@ -527,6 +536,18 @@ extern "C" {
 
 size_t mq_delete_workspace_bytes(uint64_t n) { return layout(n).total; }
 
+void mq_dml_geometry(uint64_t n, uint32_t* prefix_blocks, uint64_t* prefix_chunk_words, uint32_t* index_blocks,
+                     uint64_t* index_chunk_rows) {
+    uint32_t b;
+    uint64_t c;
+    prefix_chunks(layout(n).words, &b, &c);
+    if (prefix_blocks) *prefix_blocks = b;
+    if (prefix_chunk_words) *prefix_chunk_words = c;
+    index_chunks(n, &b, &c);
+    if (index_blocks) *index_blocks = b;
+    if (index_chunk_rows) *index_chunk_rows = c;
+}
+
 int mq_delete_plan(const int32_t* d_pos, uint64_t k, uint64_t n, uint64_t* h_deleted, uint64_t* h_bad, void* d_ws,
                    size_t ws_bytes, void* stream) {
     DevState* s;
@@ -553,7 +574,7 @@ int mq_delete_plan(const int32_t* d_pos, uint64_t k, uint64_t n, uint64_t* h_del
     }
     uint32_t blocks;
     uint64_t chunk;
-    chunks(l.words + 1, kTPB, kRankBlocks, &blocks, &chunk);
+    prefix_chunks(l.words, &blocks, &chunk);
     hipLaunchKernelGGL(k_dml_word_sums, dim3(blocks), dim3(kTPB), 0, st, bm, l.words, chunk, csum, hdr + 1);
     LAUNCHCHK("k_dml_word_sums");
     hipLaunchKernelGGL(k_dml_word_prefix, dim3(blocks), dim3(kTPB), 0, st, bm, l.words, chunk, csum, pre);
@@ -627,7 +648,7 @@ int mq_delete_index(void* d_ws, const int32_t* d_values, const uint64_t* d_posit
     hipStream_t st = (hipStream_t)stream;
     uint32_t blocks;
     uint64_t chunk;
-    chunks(n, kIdxStep, kIdxBlocks, &blocks, &chunk);
+    index_chunks(n, &blocks, &chunk);
     hipLaunchKernelGGL(k_dml_index_count, dim3(blocks), dim3(kTPB), 0, st, pos, n, chunk, bm, icnt);
     LAUNCHCHK("k_dml_index_count");
     hipLaunchKernelGGL(k_dml_index_write, dim3(blocks), dim3(kTPB), 0, st, d_values, pos, n, chunk, bm, pre, icnt, left,
@@ -678,7 +699,7 @@ int mq_insert_plan(const uint32_t* d_ins, uint64_t k, uint64_t n, uint64_t* h_ba
     }
     uint32_t blocks;
     uint64_t chunk;
-    chunks(l.words + 1, kTPB, kRankBlocks, &blocks, &chunk);
+    prefix_chunks(l.words, &blocks, &chunk);
     hipLaunchKernelGGL(k_dml_word_sums, dim3(blocks), dim3(kTPB), 0, st, bm, l.words, chunk, csum, hdr + 1);
     LAUNCHCHK("k_dml_word_sums");
     hipLaunchKernelGGL(k_dml_word_prefix, dim3(blocks), dim3(kTPB), 0, st, bm, l.words, chunk, csum, pre);

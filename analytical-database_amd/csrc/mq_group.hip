@@ -80,6 +80,9 @@ constexpr int kSegBlocks = 2048;               // chunks of the sort path's pass
 constexpr int kSegU = 4;                       // rows per lane per tile
 constexpr int kSegTile = kTPB * kSegU;
 
+// The sort path's fixed grid over the n sorted rows (k_group_heads, k_group_seg_write).
+void seg_chunks(uint64_t n, uint32_t* blocks, uint64_t* chunk) { chunks(n, kSegTile, kSegBlocks, blocks, chunk); }
+
 // The blocks' tables in the scratch, [block][slot] each; bad: [block][wave].
 struct DenseTabs {
     long long* sum;
@@ -548,7 +551,7 @@ int plan_sort(mq_group* g, const int32_t* keys, uint64_t n, const int32_t* bound
             return set_err(MQ_EINVAL, "mq_group_plan: keys [%d, %d] outside the bounds [%d, %d]", ends[0], ends[1], bounds[0],
                            bounds[1]);
     }
-    chunks(n, kSegTile, kSegBlocks, &g->blocks, &g->chunk);
+    seg_chunks(n, &g->blocks, &g->chunk);
     u64* hdr = reinterpret_cast<u64*>(g->ccnt);
     HIPCHK(hipMemsetAsync(hdr, 0, 16, st));
     hipLaunchKernelGGL(k_group_heads, dim3(g->blocks), dim3(kTPB), 0, st, g->sorted, (uint32_t)n, g->chunk, g->ccnt + 4, hdr);
@@ -573,6 +576,14 @@ void release(mq_group* g, hipStream_t st) {
 extern "C" {
 
 uint32_t mq_group_dense_slots(void) { return kDenseSlots; }
+
+void mq_group_sort_geometry(uint64_t n, uint32_t* blocks, uint64_t* chunk_rows) {
+    uint32_t b;
+    uint64_t c;
+    seg_chunks(n, &b, &c);
+    if (blocks) *blocks = b;
+    if (chunk_rows) *chunk_rows = c;
+}
 
 int mq_group_plan(const int32_t* d_keys, const int32_t* d_vals, uint64_t n, const int32_t* h_key_bounds, int path,
                   mq_group** out, uint64_t* h_groups, int* h_path, void* stream) {

@@ -135,6 +135,8 @@ _SIGS = {
     "mq_default_stream": (_vp, []),
     "mq_scan_workspace_bytes": (_sz, [_u64]),
     "mq_scan_geometry": (None, [_u64, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
+    "mq_group_sort_geometry": (None, [_u64, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
+    "mq_dml_geometry": (None, [_u64, C.POINTER(C.c_uint32), C.POINTER(_u64), C.POINTER(C.c_uint32), C.POINTER(_u64)]),
     "mq_test_set_cu_limit": (_int, [_int]),
     # data
     "mq_gen_uniform": (_int, [_vp, _u64, _u64, _u64, _vp]),

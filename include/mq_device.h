@@ -102,6 +102,17 @@ int mq_device_sync(void);
 size_t mq_scan_workspace_bytes(uint64_t n);
 /* The library's grid for a scan of n rows: blocks launched and rows per block. */
 void mq_scan_geometry(uint64_t n, uint32_t* blocks, uint64_t* rows_per_block);
+/* The fixed grids of the chunked passes, from the helpers their launches call; both need
+ * no device, and any output pointer may be NULL. A block walks its chunk in steps (1024
+ * rows, 256 bitmap words) and carries state from one step to the next.
+ * group sort path (k_group_heads, k_group_seg_write) over n rows: blocks launched and
+ * the rows in a block's chunk. */
+void mq_group_sort_geometry(uint64_t n, uint32_t* blocks, uint64_t* chunk_rows);
+/* delete / insert over n rows (an insert: n old + k new): the word prefix of the plan
+ * (k_dml_word_sums, k_dml_word_prefix: blocks, bitmap words a chunk) and the index pass
+ * of mq_delete_index (k_dml_index_count, k_dml_index_write: blocks, entries a chunk). */
+void mq_dml_geometry(uint64_t n, uint32_t* prefix_blocks, uint64_t* prefix_chunk_words,
+                     uint32_t* index_blocks, uint64_t* index_chunk_rows);
 /* Test hook (no reference counterpart; as mq_shard_join_inject_failure in mq_query.h):
  * size every grid as on a device of at most `cus` compute units, so that a column of a
  * few million rows gives each block and wave the long row runs of a 1e9-row column.

@@ -37,6 +37,55 @@ def delete_sets(n: int) -> dict:
     return out
 
 
+# ---------------------------------------------------------------------------
+# Past one step a block. The word prefix (k_dml_word_sums / _prefix) walks a chunk of bitmap
+# words in PREFIX_STEP-word steps, the index pass (k_dml_index_count / _write) a chunk of
+# entries in INDEX_STEP-entry steps; both carry a running base from step to step. The
+# chunks come from mq_dml_geometry: one step long up to 16 773 120 rows (prefix) and
+# 2 097 152 rows (index).
+# ---------------------------------------------------------------------------
+PREFIX_STEP = 256          # bitmap words per step of k_dml_word_prefix
+INDEX_STEP = 1024          # index entries per step of k_dml_index_write
+BIG_N = 2**24 + 5          # two prefix steps and nine index steps a block
+INDEX_N = [2_097_153, 4_195_333]  # the first sizes with 2 and 3 index steps a block
+BIG_SETS = ["random_50pct", "random_1pct", "first_steps", "second_steps"]
+INDEX_MULT = 1_000_003     # positions (i * INDEX_MULT) mod n: a permutation where gcd = 1
+
+
+def big_delete_set(name: str, n: int, chunk_words: int) -> np.ndarray:
+    """Sorted distinct row ids (int64) of a named delete set for the many-step sizes.
+    first_steps: in six prefix chunks every row of the first PREFIX_STEP words and none of
+    the second PREFIX_STEP words (one step's total full, the next zero), elsewhere a random
+    30 %; second_steps is its complement."""
+    rng = np.random.default_rng(3000 + n + BIG_SETS.index(name))
+    if name == "random_50pct":
+        return np.flatnonzero(rng.random(n) < 0.5)
+    if name == "random_1pct":
+        return np.flatnonzero(rng.random(n) < 0.01)
+    gone = np.random.default_rng(3000 + n).random(n) < 0.3
+    nchunks = n // (64 * chunk_words)  # whole chunks of rows
+    assert nchunks >= 6 and chunk_words >= 2 * PREFIX_STEP
+    for c in (0, 1, 7, nchunks // 2, nchunks - 2, nchunks - 1):
+        r0 = c * chunk_words * 64
+        gone[r0:r0 + PREFIX_STEP * 64] = True
+        gone[r0 + PREFIX_STEP * 64:r0 + 2 * PREFIX_STEP * 64] = False
+    if name == "first_steps":
+        return np.flatnonzero(gone)
+    if name == "second_steps":
+        return np.flatnonzero(~gone)
+    raise KeyError(name)
+
+
+def big_index(n: int, clustered: bool):
+    """A sorted index over n rows without an n-row argsort: values ascending with ties (a
+    thousand distinct), positions the permutation (i * INDEX_MULT) mod n, or the identity
+    for the clustered form."""
+    assert np.gcd(INDEX_MULT, n) == 1
+    v = np.sort(np.random.default_rng(n).integers(0, 1000, n).astype(np.int32))
+    i = np.arange(n, dtype=np.uint64)
+    return v, i if clustered else (i * np.uint64(INDEX_MULT)) % np.uint64(n)
+
+
 def position_list(ids: np.ndarray, order: str, seed: int = 0) -> np.ndarray:
     """The ids as a position list: every id twice, in the given order."""
     p = np.repeat(ids, 2)

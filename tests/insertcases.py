@@ -37,6 +37,21 @@ def insertion_points(n: int) -> dict:
     return out
 
 
+BIG_HALF_K = dc.BIG_N // 3  # k = n / 2 new rows where n + k = dmlcases.BIG_N
+
+
+def big_points(name: str, n: int, k: int) -> np.ndarray:
+    """k ascending insertion points into n old rows for the sizes past one prefix step: all
+    at the front, all appended, or sorted random points (repeats among them)."""
+    if name == "front":
+        p = np.zeros(k)
+    elif name == "append":
+        p = np.full(k, n)
+    else:
+        p = np.sort(np.random.default_rng(2000 + n + k).integers(0, n + 1, k))
+    return np.ascontiguousarray(p, dtype=np.uint32)
+
+
 def expand(old: np.ndarray, points: np.ndarray, new: np.ndarray) -> np.ndarray:
     """One column: new[j] in front of old[points[j]], equal points in their order."""
     return np.insert(old, points.astype(np.int64), new)

@@ -12,7 +12,7 @@ import pytest
 import dmlcases as dc
 from refapi import make_result, free_result_struct, mq
 
-DEVICE_API = ["mq_delete_workspace_bytes", "mq_delete_plan", "mq_delete_columns", "mq_delete_index",
+DEVICE_API = ["mq_delete_workspace_bytes", "mq_dml_geometry", "mq_delete_plan", "mq_delete_columns", "mq_delete_index",
               "mq_update_rows"]
 DROPIN_API = ["relational_delete", "relational_update"]
 
@@ -36,6 +36,54 @@ def test_workspace_size_needs_no_device():
     assert all(s > 0 for s in sizes) and sizes == sorted(sizes)
     # one bit per row and one u32 per 64 rows, plus a fixed part
     assert sizes[-1] < (2**31) * 3 // 16 + (1 << 20)
+
+
+def _geometry(lib, n):
+    pb, pc, ib, ic_ = C.c_uint32(77), C.c_uint64(77), C.c_uint32(77), C.c_uint64(77)
+    lib.mq_dml_geometry(n, C.byref(pb), C.byref(pc), C.byref(ib), C.byref(ic_))
+    return (pb.value, pc.value), (ib.value, ic_.value)
+
+
+def test_geometry_needs_no_device():
+    """(blocks, chunk) of the word prefix and of the index pass, pinned: chunks() of
+    mq_scan_common.h over the bitmap words + 1 in 256-word steps on at most 1024 blocks,
+    and over the entries in 1024-entry steps on at most 2048 blocks. The prefix takes a
+    second step a block from 16 773 121 rows on, the index pass from 2 097 153."""
+    lib = mq.load()
+    assert _geometry(lib, 16_773_120)[0] == (1024, 256)
+    assert _geometry(lib, 16_773_121)[0] == (513, 512)
+    assert _geometry(lib, 2**24 + 5) == ((513, 512), (1821, 9216))
+    assert _geometry(lib, 2_097_152)[1] == (2048, 1024)
+    assert _geometry(lib, 2_097_153)[1] == (1025, 2048)
+    assert _geometry(lib, 4_195_333)[1] == (1366, 3072)
+    assert _geometry(lib, 2**20 + 5) == ((65, 256), (1025, 1024))  # the largest of dc.SIZES: one step a block
+    assert _geometry(lib, 0) == ((1, 256), (1, 1024))
+    lib.mq_dml_geometry(5000, None, None, None, None)  # any output may be NULL
+    assert dc.BIG_N == 2**24 + 5 and dc.INDEX_N == [2_097_153, 4_195_333]
+
+
+def test_big_cases_are_what_they_say():
+    """dmlcases.big_delete_set / big_index at a small size with a two-step chunk: in the
+    picked chunks first_steps deletes every row of the first step's words and none of the
+    second's, second_steps is its complement, and big_index is a sorted index with ties
+    over a permutation."""
+    cw = 2 * dc.PREFIX_STEP
+    n = 8 * cw * 64 + 77
+    first, second = dc.big_delete_set("first_steps", n, cw), dc.big_delete_set("second_steps", n, cw)
+    assert np.array_equal(np.sort(np.concatenate([first, second])), np.arange(n))
+    gone = np.zeros(n, dtype=bool)
+    gone[first] = True
+    step = dc.PREFIX_STEP * 64
+    for c in (0, 1, 7, 4, 6):
+        assert gone[c * 2 * step:c * 2 * step + step].all() and not gone[c * 2 * step + step:(c + 1) * 2 * step].any()
+    assert 0.2 < gone[2 * 2 * step:3 * 2 * step].mean() < 0.4
+    for name, frac in (("random_50pct", 0.5), ("random_1pct", 0.01)):
+        ids = dc.big_delete_set(name, n, cw)
+        assert np.all(np.diff(ids) > 0) and abs(len(ids) / n - frac) < 0.01
+    v, p = dc.big_index(n, clustered=False)
+    assert np.all(v[1:] >= v[:-1]) and len(np.unique(v)) == 1000
+    assert np.array_equal(np.sort(p), np.arange(n, dtype=np.uint64)) and not np.array_equal(p, np.arange(n))
+    assert np.array_equal(dc.big_index(n, clustered=True)[1], np.arange(n, dtype=np.uint64))
 
 
 def test_model_is_consistent():

@@ -2,6 +2,14 @@
 relational_update in mq_query.c), every comparison exact equality with the numpy
 restatement in dmlcases.py (the workload generator's pandas statements,
 milestone5.py:127-142, 186-202; the reference itself has neither command).
+
+Which regime each size reaches: dc.SIZES (up to 2^20 + 5 rows) cover the compaction's
+tiles and alignments with one step a block in the word prefix and in the index pass, both
+of which run on fixed grids. 2 097 153 and 4 195 333 rows are the first with 2 and 3 steps
+a block in the index pass (k_dml_index_count / _write); 2^24 + 5 rows give 2 steps a block
+in the word prefix (k_dml_word_sums / _prefix) and 9 in the index pass, so the bases both
+carry from step to step are exercised. Those tests assert their regime from
+mq_dml_geometry first. mq_update_rows past one grid-stride step is in test_gpu_regimes.py.
 """
 import ctypes as C
 import mmap
@@ -89,6 +97,139 @@ def test_delete_columns_and_index(lib, n, ncols):
                 gv, gq = ov.get(np.int32, left + 2), oq.get(np.uint64, left + 2)
                 assert np.array_equal(gv[:left], wv) and np.array_equal(gq[:left], wq), tag
                 assert np.all(gv[left:] == -7) and np.all(gq[left:] == 7), tag + ("wrote past the end",)
+
+
+# ---------------------------------------------------------------------------
+# past one step a block
+#
+# The word prefix and the index pass run on fixed grids (mq_dml_geometry). At every size
+# of dc.SIZES a block's chunk is one step long, so `base += total` (k_dml_word_prefix) and
+# `base += run` (k_dml_index_write) never carry anything. dc.BIG_N gives two prefix steps
+# and nine index steps a block; dc.INDEX_N are the first sizes with 2 and 3 index steps.
+# ---------------------------------------------------------------------------
+FILL32, FILL64 = 0x5A5A5A5A, 0x5A5A5A5A5A5A5A5A  # what mq_memset(0x5A) leaves
+
+
+def dml_geometry(L, n):
+    """((prefix blocks, prefix chunk words), (index blocks, index chunk rows))"""
+    pb, pc, ib, ic_ = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+    L.mq_dml_geometry(n, C.byref(pb), C.byref(pc), C.byref(ib), C.byref(ic_))
+    return (pb.value, pc.value), (ib.value, ic_.value)
+
+
+def filled(L, count, dtype, offset_elems=0):
+    """A device buffer of `count` entries of dtype, every byte 0x5A, starting offset_elems
+    entries into its allocation."""
+    size = np.dtype(dtype).itemsize
+    d = Dev((count + offset_elems) * size + 16)
+    mq.check(L.mq_memset(d.p, 0x5A, d.nbytes, None), "mq_memset")
+    d.off = offset_elems * size
+    return d
+
+
+def two_prefix_steps(L, n):
+    """The prefix chunk in words at n rows, after asserting two steps a block there and
+    several index steps a block."""
+    (pb, pc), (ib, ic_) = dml_geometry(L, n)
+    assert pc % dc.PREFIX_STEP == 0 and pc // dc.PREFIX_STEP >= 2 and pb >= 2, (n, pb, pc)
+    assert ic_ % dc.INDEX_STEP == 0 and ic_ // dc.INDEX_STEP >= 2 and ib >= 2, (n, ib, ic_)
+    return pc
+
+
+_big = {}
+
+
+def big_case(L, name):
+    """The delete set `name` at dc.BIG_N rows and its plan's position list (shuffled, every
+    id twice) on the device; one set is kept at a time."""
+    if name not in _big:
+        _big.clear()
+        ids = dc.big_delete_set(name, dc.BIG_N, two_prefix_steps(L, dc.BIG_N))
+        _big[name] = (ids, Dev.of(dc.position_list(ids, "shuffled", seed=dc.BIG_N)))
+    return _big[name]
+
+
+def plan_on_device(L, ws, dpos, k, n):
+    deleted, bad = C.c_uint64(~0), C.c_uint64(~0)
+    rc = L.mq_delete_plan(dpos.ptr, k, n, C.byref(deleted), C.byref(bad), ws.ptr, ws.nbytes, None)
+    return rc, deleted.value, bad.value
+
+
+@pytest.fixture(scope="module")
+def big_table():
+    """Two full-range columns of dc.BIG_N rows, column 1 placed 4 bytes off a 16-byte line."""
+    cols = dc.table(dc.BIG_N, 2)
+    return cols, [Dev.of(cols[0]), Dev.of(cols[1], offset_elems=1)]
+
+
+@pytest.fixture(scope="module")
+def big_ws(lib):
+    return Dev(lib.mq_delete_workspace_bytes(dc.BIG_N))
+
+
+def check_delete_index(L, ws, n, ids, clustered, tag):
+    """mq_delete_index on the plan in ws against dc.delete_index, outputs pre-filled."""
+    v, q = dc.big_index(n, clustered)
+    wv, wq = dc.delete_index(v, q, ids, n)
+    left = n - len(ids)
+    assert len(wv) == left
+    dv, dq = Dev.of(v), Dev.of(q)
+    ov, oq = filled(L, left + 4, np.int32), filled(L, left + 4, np.uint64)
+    mq.check(L.mq_delete_index(ws.ptr, dv.ptr, dq.ptr, ov.ptr, oq.ptr, None), "mq_delete_index")
+    gv, gq = ov.get(np.int32, left + 4), oq.get(np.uint64, left + 4)
+    assert np.array_equal(gv[:left], wv), tag + ("values",)
+    assert np.array_equal(gq[:left], wq), tag + ("positions",)
+    assert np.all(gv[left:].view(np.uint32) == FILL32) and np.all(gq[left:] == FILL64), tag + ("wrote past the end",)
+
+
+@pytest.mark.parametrize("name", dc.BIG_SETS)
+def test_delete_columns_two_prefix_steps(lib, big_table, big_ws, name):
+    """mq_delete_plan + mq_delete_columns at dc.BIG_N rows, where every block of the word
+    prefix takes two steps: h_deleted and h_bad, both columns equal np.delete, nothing
+    written past n - deleted. first_steps / second_steps make one step's total full and
+    the other's zero in six chunks."""
+    n = dc.BIG_N
+    ids, dpos = big_case(lib, name)
+    cols, dcols = big_table
+    left = n - len(ids)
+    assert plan_on_device(lib, big_ws, dpos, 2 * len(ids), n) == (mq.MQ_OK, len(ids), 0), name
+    outs = [filled(lib, left + 8, np.int32, offset_elems=3 * j) for j in range(2)]
+    mq.check(lib.mq_delete_columns(big_ws.ptr, ptr_array(dcols), 2, ptr_array(outs), None), "mq_delete_columns")
+    want = dc.delete_rows(cols, ids)
+    for j in range(2):
+        got = outs[j].get(np.int32, left + 8)
+        assert np.array_equal(got[:left], want[j]), (name, j)
+        assert np.all(got[left:].view(np.uint32) == FILL32), (name, j, "wrote past the end")
+
+
+@pytest.mark.parametrize("clustered", [False, True])
+@pytest.mark.parametrize("name", dc.BIG_SETS)
+def test_delete_index_two_prefix_steps(lib, big_ws, name, clustered):
+    """mq_delete_index at dc.BIG_N rows on the same plans: the renumbering reads the word
+    prefix past its first step, and every block of the index pass takes nine steps. The
+    secondary form has tied values and the positions (i * 1 000 003) mod n; the clustered
+    form the identity."""
+    n = dc.BIG_N
+    ids, dpos = big_case(lib, name)
+    assert plan_on_device(lib, big_ws, dpos, 2 * len(ids), n) == (mq.MQ_OK, len(ids), 0), name
+    check_delete_index(lib, big_ws, n, ids, clustered, (name, clustered))
+
+
+@pytest.mark.parametrize("n,steps", [(dc.INDEX_N[0], 2), (dc.INDEX_N[1], 3)])
+def test_delete_index_first_sizes_past_one_step(lib, n, steps):
+    """mq_delete_index at the first sizes where a block of the index pass takes 2 and 3
+    steps (today the last chunk holds 1 row and 2053 rows: a lone row, two whole steps and
+    a ragged one), half of the rows deleted."""
+    (_, _), (ib, ic_) = dml_geometry(lib, n)
+    assert ic_ % dc.INDEX_STEP == 0 and ic_ // dc.INDEX_STEP >= steps and ib >= 2, (n, ib, ic_)
+    assert (n - (ib - 1) * ic_) % dc.INDEX_STEP != 0, (n, ib, ic_)  # the last chunk ends in a ragged step
+    assert dml_geometry(lib, dc.INDEX_N[0] - 1)[1][1] == dc.INDEX_STEP  # one row fewer: one step a block
+    ids = dc.big_delete_set("random_50pct", n, 0)
+    ws = Dev(lib.mq_delete_workspace_bytes(n))
+    dpos = Dev.of(dc.position_list(ids, "shuffled", seed=n))
+    assert plan_on_device(lib, ws, dpos, 2 * len(ids), n) == (mq.MQ_OK, len(ids), 0)
+    for clustered in (False, True):
+        check_delete_index(lib, ws, n, ids, clustered, (n, clustered))
 
 
 @pytest.mark.parametrize("n", [1, 64, 257, 8193, 100_003])

@@ -1,6 +1,14 @@
 """Grouped aggregates on gfx950 (csrc/mq_group.hip; group_aggregate in mq_query.c), every
 comparison exact equality with the numpy restatement in groupcases.py (the reference has
 no such operator).
+
+Which regime each size reaches: gc.SIZES (up to 300 001 rows) cover both paths, the dense
+path's tiles and the sort path with one 1024-row tile a block of its fixed grid, where no
+run is carried from tile to tile. 2 097 153 rows are the first with two tiles a block (a
+last chunk of one row), 4 195 333 rows give three (a last chunk that ends in a 5-row
+tile): there k_group_seg_write carries the open run across tiles, meets tiles with no
+head, and closes carried runs with a plain store or with atomics. Each of those tests
+asserts its regime from mq_group_sort_geometry first.
 """
 import ctypes as C
 
@@ -185,6 +193,102 @@ def test_32_plans_on_32_streams(lib, S):
         run(lib, dk.ptr, dv.ptr, n, AUTO, want, ("after the frees", ks))
     for sp in streams:
         mq.check(lib.mq_stream_destroy(sp))
+
+
+# ---------------------------------------------------------------------------
+# the sort path past one tile a block
+#
+# k_group_heads / k_group_seg_write run on a fixed grid (mq_group_sort_geometry): up to
+# 2 097 152 rows a block's chunk is one 1024-row tile, so the sizes above never carry a run
+# from one tile to the next. gc.SORT_N gives every block three tiles (the last chunk a
+# ragged one), gc.SORT_N_TWO_TILES is the first size with two.
+# ---------------------------------------------------------------------------
+FILL = {4: 0x5A5A5A5A, 8: 0x5A5A5A5A5A5A5A5A}  # what mq_memset(0x5A) leaves in an entry
+
+
+def sort_geometry(L, n):
+    b, c = C.c_uint32(), C.c_uint64()
+    L.mq_group_sort_geometry(n, C.byref(b), C.byref(c))
+    return b.value, c.value
+
+
+def run_filled(L, dk, dv, n, path, want, tag, skip=()):
+    """run() with the outputs pre-filled with 0x5A bytes on the device; returns the path."""
+    rc, h, g, taken = plan(L, dk, dv, n, path)
+    assert rc == mq.MQ_OK and h, tag + (mq.load().mq_last_error(),)
+    assert g == len(want[0]), tag
+    outs = {nm: None if nm in skip else Dev((g + PAD) * np.dtype(DTYPE[nm]).itemsize) for nm in NAMES}
+    for o in outs.values():
+        if o:
+            mq.check(L.mq_memset(o.ptr, 0x5A, o.nbytes, None), "mq_memset")
+    mq.check(write(L, h, outs), "mq_group_write")
+    for nm, w in zip(NAMES, want):
+        if outs[nm] is None:
+            continue
+        got = outs[nm].get(DTYPE[nm], g + PAD)
+        assert np.array_equal(got[:g], w), tag + (nm,)
+        assert np.all(got[g:].view(f"u{got.itemsize}") == FILL[got.itemsize]), tag + (nm, "wrote past the groups")
+    mq.check(L.mq_group_free(h), "mq_group_free")
+    return taken
+
+
+def sort_regime(L, n, tiles):
+    """The chunk of the sort path at n rows, after asserting `tiles` tiles a block, more
+    than one block and a last chunk that ends in a ragged tile."""
+    blocks, chunk = sort_geometry(L, n)
+    assert chunk % gc.SEG_TILE == 0 and chunk // gc.SEG_TILE >= tiles and blocks >= 2, (n, blocks, chunk)
+    last = n - (blocks - 1) * chunk
+    assert 0 < last <= chunk and last % gc.SEG_TILE != 0, (n, blocks, chunk, last)
+    return chunk
+
+
+@pytest.mark.parametrize("runset", gc.RUN_SETS)
+def test_sort_path_three_tiles_a_block(lib, runset):
+    """SORT forced at gc.SORT_N rows: keys, count, sum, min, max and the plan's group count
+    equal the restatement, nothing is written past the groups. The key columns are built
+    from the run lengths of the sorted keys (groupcases.runs_of): one key (every chunk after
+    the first has no head and emits with atomics onto group 0), all distinct (1024 heads a
+    tile), runs of exactly one tile and of exactly one chunk starting on, one row after and
+    one row before the edges, mixed lengths, and one run over 90 % of the rows. Values are
+    full-range with INT32_MIN / INT32_MAX planted around every tile edge; the one-key column
+    also sums all-INT32_MAX and all-INT32_MIN values (|sum| about 9e15). all_distinct under
+    AUTO reports SORT; mixed also runs without the count and sum outputs."""
+    n = gc.SORT_N
+    chunk = sort_regime(lib, n, 3)
+    runs = gc.runs_of(runset, n, chunk)
+    keys, order = gc.keys_from_runs(runs, seed=n + len(runset))
+    assert len(keys) == n
+    dk = Dev.of(keys)
+    vsets = [gc.planted_values(runs, order, seed=7)]
+    if runset == "one_key":
+        vsets += [gc.values_of("all_max", keys), gc.values_of("all_min", keys)]
+    for i, vals in enumerate(vsets):
+        want = gc.group(keys, vals)
+        assert len(want[0]) == len(runs) and np.array_equal(want[1], runs.astype(np.uint64))
+        dv = Dev.of(vals, offset_elems=i & 1)
+        assert run_filled(lib, dk.ptr, dv.ptr, n, SORT, want, (runset, i)) == SORT
+        if runset == "all_distinct":
+            assert run_filled(lib, dk.ptr, dv.ptr, n, AUTO, want, (runset, "AUTO")) == SORT
+        if runset == "mixed":
+            run_filled(lib, dk.ptr, dv.ptr, n, SORT, want, (runset, "no count, no sum"), skip=("count", "sum"))
+    if runset == "one_key":
+        assert abs(int(want[2][0])) > 9 * 10**15
+
+
+def test_sort_path_first_size_with_two_tiles(lib):
+    """gc.SORT_N_TWO_TILES rows: two tiles a block and a last chunk of one row, on the
+    mixed run lengths."""
+    n = gc.SORT_N_TWO_TILES
+    chunk = sort_regime(lib, n, 2)
+    blocks, _ = sort_geometry(lib, n)
+    assert n - (blocks - 1) * chunk == 1 and sort_geometry(lib, n - 1)[1] == gc.SEG_TILE
+    runs = gc.runs_of("mixed", n, chunk)
+    keys, order = gc.keys_from_runs(runs, seed=n)
+    vals = gc.planted_values(runs, order, seed=8)
+    want = gc.group(keys, vals)
+    assert len(want[0]) == len(runs)
+    dk, dv = Dev.of(keys, offset_elems=1), Dev.of(vals)
+    assert run_filled(lib, dk.ptr, dv.ptr, n, SORT, want, ("mixed", n)) == SORT
 
 
 # ---------------------------------------------------------------------------

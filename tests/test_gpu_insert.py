@@ -2,6 +2,13 @@
 comparison exact equality with the numpy restatement in insertcases.py: the reference's
 insert_row (db_manager.c:164-199) issued once per row, with the clustered order and the
 sorted indexes maintained as the workload generator expects (milestone5.py:40-78).
+
+Which regime each size reaches: ic.SIZES (up to 2^20 + 5 old rows) cover the expansion's
+tiles and alignments with one step a block in the plan's word prefix. At n + k = 2^24 + 5
+slots every block of the prefix takes two steps (asserted from mq_dml_geometry), for
+mq_insert_columns and mq_insert_index alike. The grid-stride kernels (k_ins_points,
+k_ins_slots, k_ins_positions, k_ins_index) take one loop step at every size here; past one
+step they run in test_gpu_regimes.py under a CU limit.
 """
 import ctypes as C
 
@@ -12,7 +19,8 @@ import dmlcases as dc
 import insertcases as ic
 from devbuf import Dev
 from refapi import make_result, free_result_struct, mq, take
-from test_gpu_dml import Tbl, check_index, lib, memfd_array, ptr_array  # noqa: F401 (lib: fixture)
+from test_gpu_dml import (FILL32, FILL64, Tbl, check_index, filled, lib, memfd_array, ptr_array,  # noqa: F401 (lib: fixture)
+                          two_prefix_steps)
 
 pytestmark = pytest.mark.gpu
 
@@ -88,8 +96,11 @@ def test_insert_index(lib, n):
     """An index with many equal values, the positions among them shuffled; the new entries
     carry rows n.. (an append) or their slots of a sorted insert, whose points renumber the
     old positions. mq_insert_slots / mq_insert_positions give those rows."""
+    check_insert_index(lib, n, max(n // 3, 7))
+
+
+def check_insert_index(lib, n, k):
     rng = np.random.default_rng(n)
-    k = max(n // 3, 7)
     key = (rng.permutation(n) % 11).astype(np.int32)
     shuf = rng.permutation(n)
     p = shuf[np.argsort(key[shuf], kind="stable")]
@@ -122,6 +133,74 @@ def test_insert_index(lib, n):
         assert np.array_equal(gv[:n + k], wv) and np.array_equal(gp[:n + k], wp)
         assert np.all(gv[n + k:] == -7) and np.all(gp[n + k:] == 7)
         assert np.array_equal(np.sort(gp[:n + k]), np.arange(n + k, dtype=np.uint64))
+
+
+# ---------------------------------------------------------------------------
+# past one step a block
+#
+# mq_insert_plan shares the delete's word prefix (k_dml_word_sums / _prefix) over the
+# n + k output slots. At every size of ic.SIZES a block's chunk of bitmap words is one
+# step long; at n + k = dc.BIG_N every block takes two and `base += total` carries the
+# first step's count into the second (mq_dml_geometry, asserted by two_prefix_steps).
+# ---------------------------------------------------------------------------
+BIG_K = {"front": 1000, "append": 1000, "random": 1000, "half": ic.BIG_HALF_K}
+
+
+@pytest.mark.parametrize("name", list(BIG_K))
+def test_insert_columns_two_prefix_steps(lib, name):
+    """mq_insert_plan + mq_insert_columns at n + k = dc.BIG_N slots: 1000 new rows at the
+    front, appended and at random points, and k = n / 2 at sorted random points; one
+    aligned column and one 4 bytes off, each equal to the restatement, nothing written past
+    the end."""
+    k = BIG_K[name]
+    n = dc.BIG_N - k
+    two_prefix_steps(lib, n + k)
+    points = ic.big_points(name, n, k)
+    expand_and_check(lib, dc.table(n, 2), points, dc.table(k, 2, seed=1), in_off=lambda j: j, tag=(name,))
+
+
+@pytest.mark.parametrize("name", ["random", "half"])
+def test_insert_index_two_prefix_steps(lib, name):
+    """mq_insert_index with renumbering at n + k = dc.BIG_N entries, on dc.big_index's tied
+    values and permuted positions, against ic.insert_index. The table's rows were
+    interleaved by a sorted insert of their own (mq_insert_slots gives the new rows' slots,
+    mq_insert_positions files them in the index's order)."""
+    k = BIG_K[name]
+    n = dc.BIG_N - k
+    m = n + k
+    two_prefix_steps(lib, m)
+    rng = np.random.default_rng(k)
+    v, p = dc.big_index(n, clustered=False)
+    # the indexed column's new values, batch order; for k = n / 2 already ascending, so that
+    # neither the test nor the model sorts millions of rows
+    new_v = rng.integers(-2, 1002, k).astype(np.int32)
+    if name == "half":
+        new_v.sort()
+    order = np.argsort(new_v, kind="stable").astype(np.uint64)
+    points = np.searchsorted(v, new_v[order.astype(np.int64)], side="right").astype(np.uint32)
+    # the table's clustered keys: ascending old keys, new keys in batch order
+    tkeys_old = (np.arange(n, dtype=np.int64) * 50 // n).astype(np.int32)
+    tkeys_new = rng.integers(-5, 55, k).astype(np.int32)
+    tpoints, slots = ic.new_slots(tkeys_old, tkeys_new)
+    torder = np.argsort(tkeys_new, kind="stable").astype(np.uint64)
+    ws = Dev(lib.mq_insert_workspace_bytes(n, k))
+    assert plan(lib, ws, points, n) == (mq.MQ_OK, 0)
+    dv, dp, dnv = Dev.of(v), Dev.of(p), Dev.of(new_v[order.astype(np.int64)])
+    dtp, dto, dord = Dev.of(tpoints), Dev.of(torder), Dev.of(order)
+    dslots, dnp = Dev.of(np.full(k + 1, 5, np.uint64)), Dev.of(np.full(k + 1, 5, np.uint64))
+    mq.check(lib.mq_insert_slots(dtp.ptr, dto.ptr, k, dslots.ptr, None), "mq_insert_slots")
+    got = dslots.get(np.uint64, k + 1)
+    assert np.array_equal(got[:k], slots) and got[k] == 5
+    mq.check(lib.mq_insert_positions(dslots.ptr, n, dord.ptr, k, dnp.ptr, None), "mq_insert_positions")
+    got = dnp.get(np.uint64, k + 1)
+    assert np.array_equal(got[:k], slots[order.astype(np.int64)]) and got[k] == 5
+    ov, op = filled(lib, m + 4, np.int32), filled(lib, m + 4, np.uint64)
+    mq.check(lib.mq_insert_index(ws.ptr, dv.ptr, dp.ptr, dnv.ptr, dnp.ptr, dtp.ptr, k, ov.ptr, op.ptr, None),
+             "mq_insert_index")
+    wv, wp = ic.insert_index(v, p, new_v, slots, tpoints)
+    gv, gp = ov.get(np.int32, m + 4), op.get(np.uint64, m + 4)
+    assert np.array_equal(gv[:m], wv) and np.array_equal(gp[:m], wp)
+    assert np.all(gv[m:].view(np.uint32) == FILL32) and np.all(gp[m:] == FILL64)
 
 
 def test_error_codes(lib):

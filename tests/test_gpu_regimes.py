@@ -7,9 +7,10 @@ wave-chunks of shared select and of k_group_dense then run only in the 1e9-row t
 which check properties on uniform data. mq_test_set_cu_limit (mq_device.h) lowers the CU
 count the geometry uses; with 1, 2 or 7 CUs a column of 0.3-4 M rows gives each block
 what a 1e9-row column gives it on the whole device. The grid-stride operators (fetch,
-add / sub, gather, histogram, hashset lookup) take a second step of their loops only past
-524 288 work items on the whole device; under a limit a few thousand are enough. Expected
-values come from numpy, the refcpu oracle and groupcases.py; each test asserts first that
+add / sub, gather, histogram, hashset lookup, and the insert and update kernels of
+mq_dml.hip) take a second step of their loops only past 524 288 work items on the whole
+device; under a limit a few thousand are enough. Expected values come from numpy, the
+refcpu oracle, groupcases.py, dmlcases.py and insertcases.py; each test asserts first that
 its regime is reached.
 """
 import ctypes as C
@@ -613,7 +614,82 @@ def test_hashset_lookup_many_sweeps(lib, refcpu, limit):
 
 
 # ---------------------------------------------------------------------------
-# f. the hook itself
+# f. the grid-stride insert and update operators: k_ins_points, k_ins_slots,
+#    k_ins_positions, k_ins_index, k_dml_update
+#
+# The same stream_grid loops: with one limited CU the grid has lanes(1) = 2048 lanes, and a
+# few tens of thousands of items give every lane more than 10 steps and a ragged last one.
+# ---------------------------------------------------------------------------
+def _many_steps(*counts):
+    S = lanes(1)
+    for c in counts:
+        assert c > 10 * S and c % S not in (0, S - 1), (c, S)  # every lane past 10 steps; a ragged last step
+
+
+def test_insert_points_many_steps(lib, limit):
+    """mq_insert_points of 25 003 sorted new keys into 60 001 old ones with duplicates and
+    both INT32 ends, against np.searchsorted."""
+    limit(1)
+    n, k = 60_001, 25_003
+    _many_steps(k)
+    rng = np.random.default_rng(61)
+    old = rng.integers(-4000, 4000, n) * 3
+    old[:2], old[-2:] = I32MIN, I32MAX
+    old = np.sort(old).astype(np.int32)
+    new = np.concatenate([rng.integers(-12_500, 12_500, k - 6), [I32MIN, I32MIN, I32MAX, I32MAX, -12_001, 12_001]])
+    new = np.sort(new).astype(np.int32)
+    dold, dnew, dins = Dev.of(old), Dev.of(new), Dev(4 * (k + PAD))
+    _refill(lib, dins)
+    mq.check(lib.mq_insert_points(dold.ptr, n, dnew.ptr, k, dins.ptr, None), "mq_insert_points")
+    got = dins.get(np.uint32, k + PAD)
+    assert np.array_equal(got[:k], np.searchsorted(old, new, side="right"))
+    assert np.all(got[k:] == SENT), "wrote past the points"
+
+
+def test_insert_index_slots_positions_many_steps(lib, limit):
+    """test_gpu_insert's index merge (mq_insert_slots with an order, mq_insert_positions
+    from slots and from a base, mq_insert_index with and without renumbering) with 30 011
+    new entries on 45 007 old ones: 75 018 slots, 36 steps a lane. Then mq_insert_slots
+    without an order."""
+    from test_gpu_insert import check_insert_index
+    limit(1)
+    n, k = 45_007, 30_011
+    _many_steps(k, n + k)
+    check_insert_index(lib, n, k)
+    ins = np.sort(np.random.default_rng(67).integers(0, n + 1, k)).astype(np.uint32)
+    dins, dslots = Dev.of(ins), Dev(8 * (k + PAD))
+    _refill(lib, dslots)
+    mq.check(lib.mq_insert_slots(dins.ptr, None, k, dslots.ptr, None), "mq_insert_slots")
+    got = dslots.get(np.uint64, k + PAD)
+    assert np.array_equal(got[:k], ins.astype(np.uint64) + np.arange(k, dtype=np.uint64))
+    assert np.all(got[k:] == np.uint64(0x5A5A5A5A5A5A5A5A)), "wrote past the slots"
+
+
+def test_update_rows_many_steps(lib, limit):
+    """mq_update_rows with 40 009 ids (repeats, five of them outside the column) on 100 003
+    rows: the listed rows change, no other does, the ids outside are counted."""
+    import dmlcases as dc
+    limit(1)
+    n, k = 100_003, 40_009
+    _many_steps(k)
+    rng = np.random.default_rng(71)
+    col = dc.table(n, 1)[0]
+    ids = rng.integers(0, n, 30_003).astype(np.int32)
+    ids = np.concatenate([ids, ids[::3]])  # repeats
+    assert len(ids) == k - 5
+    wild = np.concatenate([ids, [-1, n, n + 1, I32MAX, I32MIN]]).astype(np.int32)
+    rng.shuffle(wild)
+    # the steps touch disjoint rows: a step that repeated another would leave rows unchanged
+    assert len(np.unique(wild[-lanes(1):])) > lanes(1) // 2
+    d, dp, bad = Dev.of(np.concatenate([col, [4242, 4242]]).astype(np.int32)), Dev.of(wild), Dev.of(np.array([99], np.uint64))
+    mq.check(lib.mq_update_rows(d.ptr, n, dp.ptr, k, -10, bad.ptr, None), "mq_update_rows")
+    got = d.get(np.int32, n + 2)
+    assert np.array_equal(got[:n], dc.update_rows(col, ids, -10)) and np.all(got[n:] == 4242)
+    assert bad.get(np.uint64, 1)[0] == 5
+
+
+# ---------------------------------------------------------------------------
+# g. the hook itself
 # ---------------------------------------------------------------------------
 def test_cu_limit_restores_and_never_raises(lib, limit, hardware):
     """After mq_test_set_cu_limit(0) mq_scan_geometry answers as before any limit; a

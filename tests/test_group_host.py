@@ -12,7 +12,7 @@ import pytest
 import groupcases as gc
 from refapi import make_column, mq
 
-DEVICE_API = ["mq_group_dense_slots", "mq_group_plan", "mq_group_write", "mq_group_free"]
+DEVICE_API = ["mq_group_dense_slots", "mq_group_sort_geometry", "mq_group_plan", "mq_group_write", "mq_group_free"]
 DROPIN_API = ["group_aggregate"]
 
 
@@ -35,6 +35,51 @@ def test_dense_slots_is_a_positive_constant():
     lib = mq.load()
     s = lib.mq_group_dense_slots()
     assert s > 0 and lib.mq_group_dense_slots() == s
+
+
+def _sort_geometry(lib, n):
+    b, c = C.c_uint32(77), C.c_uint64(77)
+    lib.mq_group_sort_geometry(n, C.byref(b), C.byref(c))
+    return b.value, c.value
+
+
+def test_sort_geometry_needs_no_device():
+    """(blocks, chunk rows) of the sort path's fixed grid, pinned: chunks() of
+    mq_scan_common.h with 1024-row tiles and at most 2048 blocks. A block takes a second
+    tile from 2 097 153 rows on."""
+    lib = mq.load()
+    assert _sort_geometry(lib, 4_195_333) == (1366, 3072)
+    assert _sort_geometry(lib, 2_097_152) == (2048, 1024)
+    assert _sort_geometry(lib, 2_097_153) == (1025, 2048)
+    assert _sort_geometry(lib, 300_001) == (293, 1024)  # the largest of gc.SIZES: one tile a block
+    assert _sort_geometry(lib, 1) == (1, 1024) and _sort_geometry(lib, 0) == (1, 1024)
+    lib.mq_group_sort_geometry(5000, None, None)  # either output may be NULL
+    assert (gc.SORT_N, gc.SORT_N_TWO_TILES) == (4_195_333, 2_097_153)
+
+
+def test_sort_run_sets_are_what_they_say():
+    """groupcases.runs_of / keys_from_runs / planted_values at a small size: the run
+    lengths sum to n, a stable sort of the keys has exactly those runs, both INT32 ends are
+    keys, and the values carry both extremes at tile edges of the sorted sequence."""
+    n, chunk = 20_011, 3 * gc.SEG_TILE
+    for name in gc.RUN_SETS:
+        runs = gc.runs_of(name, n, chunk)
+        assert runs.sum() == n and runs.min() >= 1, name
+        keys, order = gc.keys_from_runs(runs, seed=3)
+        k, count = gc.group(keys, keys)[:2]
+        assert np.array_equal(count, runs.astype(np.uint64)), name
+        assert k[0] == gc.I32_MIN and (len(k) == 1 or k[-1] == gc.I32_MAX), name
+        assert np.array_equal(keys[order], np.repeat(k, runs)), name
+        sv = gc.planted_values(runs, order, seed=4)[order]
+        assert {int(sv[gc.SEG_TILE - 1]), int(sv[gc.SEG_TILE])} == {gc.I32_MIN, gc.I32_MAX}, name
+    starts = lambda name: np.concatenate([[0], np.cumsum(gc.runs_of(name, n, chunk))[:-1]])
+    assert np.all(starts("tile_runs") % gc.SEG_TILE == 0)
+    assert np.all(starts("tile_runs_plus_1")[1:] % gc.SEG_TILE == 1)
+    assert np.all(starts("tile_runs_minus_1")[1:] % gc.SEG_TILE == gc.SEG_TILE - 1)
+    assert np.all(starts("chunk_runs_plus_1")[1:] % chunk == 1)
+    assert np.all(starts("chunk_runs_minus_1")[1:] % chunk == chunk - 1)
+    assert gc.runs_of("skewed", n, chunk).max() == n * 9 // 10
+    assert set(gc.runs_of("mixed", n, chunk)[:-1].tolist()) <= set(gc.MIXED_RUNS)
 
 
 def test_model_is_consistent():
