@@ -37,22 +37,38 @@
 //                        per run in LDS. A run inside one tile is stored directly; the run
 //                        left open at a tile's end is carried to the next tile; a run that
 //                        crosses a chunk edge is combined with atomics onto the identity.
+//
+// mq_group_where_plan is the same operator over the rows for which a
+// conjunction of range predicates holds (mq_where.hip's definition), on the same handle:
+//   k_group_where_dense: k_where_agg's stream (mq_where_common.h: the predicate columns,
+//                        then of the key and the value column only the 128-byte lines in
+//                        which a row survived) feeding k_group_dense's table, rows whose
+//                        bit is set only; a wave tile whose surviving rows share one key
+//                        (all 256 of them, or the live part of a partly live tile) joins
+//                        the run fold. The fold, the rank and the write kernels above
+//                        serve it unchanged.
+//   sort path          : mq_where_positions, the keys and the values of the K matching rows
+//                        gathered with mq_fetch into two buffers, then the sort path above
+//                        on them; the handle owns the gathered values.
 
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdint>
 #include <new>
+#include <type_traits>
 
 #include "mq_common.h"
 #include "mq_device.h"
 #include "mq_scan_common.h"
+#include "mq_where_common.h"
 
 struct mq_group {
     int path;
     int dev;
     uint64_t n, groups;
     const int32_t* vals;
+    int32_t* own_vals;   // mq_group_where_plan's sort path: the gathered values (vals points here)
     hipStream_t stream;  // of the last call that queued work on the buffers below
     // dense: the folded table
     int32_t lo;
@@ -74,6 +90,7 @@ using u64 = unsigned long long;
 // 2048 slots x 20 B = 40 KiB of LDS a block: 4 blocks (16 waves) a CU in 160 KiB.
 constexpr uint32_t kDenseSlots = 2048;
 constexpr int kGrpU = 4;                       // tiles of each column in flight per thread
+constexpr int kGwU = 4;                        // the same under predicates (k_group_where_dense)
 constexpr int kFoldSlots = 16;                 // slots per fold workgroup
 constexpr int kFoldParts = kTPB / kFoldSlots;  // block strides per slot
 constexpr int kSegBlocks = 2048;               // chunks of the sort path's passes
@@ -238,6 +255,145 @@ __global__ __launch_bounds__(kTPB, 4) void k_group_dense(const int* keys, const 
     }
 }
 
+// k_group_dense over the rows that survive the predicates of `a`: live_tiles gives each lane
+// its rows' nibble per tile, one ballot per tile says which 128-byte lines of the key and the
+// value column hold a survivor, and only those are requested (a tile without one issues
+// nothing). Keys of rows whose bit is clear are never looked at.
+template <bool VEC>
+__global__ __launch_bounds__(kTPB, 4) void k_group_where_dense(WhereArgs a, const int* keys, const int* vals, uint64_t n,
+                                                               uint64_t rows_per_block, int32_t lo, uint32_t range,
+                                                               DenseTabs out) {
+    __shared__ uint32_t s_cnt[kDenseSlots];
+    __shared__ u64 s_sum[kDenseSlots];
+    __shared__ int s_mn[kDenseSlots];
+    __shared__ int s_mx[kDenseSlots];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        s_cnt[s] = 0u;
+        s_sum[s] = 0ull;
+        s_mn[s] = INT_MAX;
+        s_mx[s] = INT_MIN;
+    }
+    __syncthreads();
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    uint32_t nbad = 0;  // live rows only
+    // the wave's run of tiles whose surviving rows all share run_key, folded per lane
+    int run_key = 0;
+    bool run_open = false;  // wave-uniform
+    uint32_t r_cnt = 0;
+    long long r_sum = 0;
+    int r_mn = INT_MAX, r_mx = INT_MIN;
+
+    auto update = [&](int k, int v) {
+        const uint32_t s = (uint32_t)k - (uint32_t)lo;  // a key below lo wraps past range
+        if (s < range) {
+            atomicAdd(&s_cnt[s], 1u);
+            atomicAdd(&s_sum[s], (u64)(long long)v);
+            atomicMin(&s_mn[s], v);
+            atomicMax(&s_mx[s], v);
+        } else {
+            nbad++;
+        }
+    };
+    auto flush = [&]() {  // wave-uniform
+        const uint32_t c = (uint32_t)wave_sum_u64(r_cnt);  // <= the rows of the block's chunk < 2^31
+        const long long sm = wave_sum_i64(r_sum);
+        const int mn = wave_min(r_mn), mx = wave_max(r_mx);
+        if (lane == 0) {
+            const uint32_t s = (uint32_t)run_key - (uint32_t)lo;
+            if (s < range) {
+                atomicAdd(&s_cnt[s], c);
+                atomicAdd(&s_sum[s], (u64)sm);
+                atomicMin(&s_mn[s], mn);
+                atomicMax(&s_mx[s], mx);
+            } else {
+                nbad += c;
+            }
+        }
+        run_open = false;
+        r_cnt = 0;
+        r_sum = 0;
+        r_mn = INT_MAX;
+        r_mx = INT_MIN;
+    };
+    // A full tile with a survivor in the wave (b: the lanes that hold one); k and v are loaded
+    // in the lanes whose line is live, so in every lane with a bit set.
+    auto consume = [&](int4 k, int4 v, uint32_t live, u64 b) {
+        const int kf = live & 1u ? k.x : live & 2u ? k.y : live & 4u ? k.z : k.w;  // the lane's first surviving key
+        const int k0 = __builtin_amdgcn_readlane(kf, __builtin_ctzll(b));
+        const bool same = live == 0u || ((!(live & 1u) || k.x == k0) && (!(live & 2u) || k.y == k0) &&
+                                         (!(live & 4u) || k.z == k0) && (!(live & 8u) || k.w == k0));
+        if (__all(same)) {  // the surviving rows of the wave's 256 share one key: into the run
+            if (run_open && k0 != run_key) flush();
+            run_key = k0;
+            run_open = true;
+            r_cnt += (uint32_t)__popc(live);
+            r_sum += (live & 1u ? (long long)v.x : 0ll) + (live & 2u ? (long long)v.y : 0ll) +
+                     (live & 4u ? (long long)v.z : 0ll) + (live & 8u ? (long long)v.w : 0ll);
+            r_mn = min(r_mn, min(min(live & 1u ? v.x : INT_MAX, live & 2u ? v.y : INT_MAX),
+                                 min(live & 4u ? v.z : INT_MAX, live & 8u ? v.w : INT_MAX)));
+            r_mx = max(r_mx, max(max(live & 1u ? v.x : INT_MIN, live & 2u ? v.y : INT_MIN),
+                                 max(live & 4u ? v.z : INT_MIN, live & 8u ? v.w : INT_MIN)));
+        } else if (__all(live == 15u)) {  // k_group_dense's tile
+            update(k.x, v.x);
+            update(k.y, v.y);
+            update(k.z, v.z);
+            update(k.w, v.w);
+        } else {
+            if (live & 1u) update(k.x, v.x);
+            if (live & 2u) update(k.y, v.y);
+            if (live & 4u) update(k.z, v.z);
+            if (live & 8u) update(k.w, v.w);
+        }
+    };
+    // U full tiles: every key and value load of the iteration is issued before the first use
+    auto tiles = [&](auto uc, uint64_t t) {
+        constexpr int U = decltype(uc)::value;
+        const uint64_t row = t + (uint64_t)tid * 4;
+        uint32_t live[U];
+        live_tiles<VEC, U>(a, row, lane, live);
+        u64 b[U];
+        int4 k[U], v[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            b[u] = __ballot(live[u] != 0u);
+            if (b[u] != 0 && line_live(b[u], lane)) k[u] = load4_nt<VEC>(keys + row + (uint64_t)u * kTileRows);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (b[u] != 0 && line_live(b[u], lane)) v[u] = load4_nt<VEC>(vals + row + (uint64_t)u * kTileRows);
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (b[u] != 0) consume(k[u], v[u], live[u], b[u]);  // wave-uniform
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)kGwU * kTileRows <= end; t += (uint64_t)kGwU * kTileRows)
+        tiles(std::integral_constant<int, kGwU>{}, t);
+    for (; t + kTileRows <= end; t += kTileRows) tiles(std::integral_constant<int, 1>{}, t);
+    if (t < end) {  // the column's ragged tile: row by row, none past the end
+        const uint64_t row = t + (uint64_t)tid * 4;
+        const uint32_t live = live_ragged(a, row, end);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (live & (1u << e)) update(keys[row + e], vals[row + e]);
+    }
+    if (run_open) flush();
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) out.bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * range;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        out.cnt[base + s] = s_cnt[s];
+        out.sum[base + s] = (long long)s_sum[s];
+        out.mn[base + s] = s_mn[s];
+        out.mx[base + s] = s_mx[s];
+    }
+}
+
 __global__ __launch_bounds__(kTPB) void k_group_fold(DenseTabs in, uint32_t blocks, uint32_t range, FinalTab f) {
     __shared__ u64 p_cnt[kFoldParts][kFoldSlots];
     __shared__ long long p_sum[kFoldParts][kFoldSlots];
@@ -303,6 +459,17 @@ __global__ __launch_bounds__(kTPB) void k_group_rank(FinalTab f, uint32_t range,
         f.hdr[0] = total;
         f.hdr[1] = s_b[0] + s_b[1] + s_b[2] + s_b[3];
     }
+}
+
+// One block: *rows = the sum of the slots' counts.
+__global__ __launch_bounds__(kTPB) void k_group_rows(FinalTab f, uint32_t range, u64* __restrict__ rows) {
+    __shared__ u64 s_r[kWaves];
+    u64 c = 0;
+    for (uint32_t s = threadIdx.x; s < range; s += kTPB) c += f.cnt[s];
+    c = wave_sum_u64(c);
+    if ((threadIdx.x & 63) == 0) s_r[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) *rows = s_r[0] + s_r[1] + s_r[2] + s_r[3];
 }
 
 __global__ __launch_bounds__(kTPB) void k_group_dense_write(FinalTab f, uint32_t range, int32_t lo,
@@ -504,18 +671,48 @@ int launch_dense(const DevState* s, const int32_t* keys, const int32_t* vals, ui
     return MQ_OK;
 }
 
-int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_t* vals, uint64_t n, hipStream_t st) {
+template <bool VEC>
+int launch_where_dense(const DevState* s, const WhereArgs& a, const int32_t* keys, const int32_t* vals, uint64_t n,
+                       int32_t lo, uint32_t range, void** scratch_out, DenseTabs* tabs, uint32_t* blocks_out,
+                       hipStream_t st) {
+    uint32_t g;
+    uint64_t rpb;
+    geometry(s, n, reinterpret_cast<const void*>(&k_group_where_dense<VEC>), &g, &rpb, (uint64_t)kGwU * kTileRows);
+    void* scratch = pool_alloc(dense_scratch_bytes(g, range));
+    if (!scratch) return set_err(MQ_ENOMEM, "mq_group_where_plan: scratch allocation failed");
+    *tabs = dense_tabs(scratch, g, range);
+    *scratch_out = scratch;
+    *blocks_out = g;
+    hipLaunchKernelGGL((k_group_where_dense<VEC>), dim3(g), dim3(kTPB), 0, st, a, keys, vals, n, rpb, lo, range, *tabs);
+    LAUNCHCHK("k_group_where_dense");
+    return MQ_OK;
+}
+
+// The dense path of both plans; w: the folded predicates of mq_group_where_plan (wvec:
+// whether their columns are all 16-byte aligned), or NULL; rows: NULL, or where the sum of
+// the groups' counts goes.
+int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_t* vals, uint64_t n, hipStream_t st,
+               const WhereArgs* w = nullptr, bool wvec = false, uint64_t* rows = nullptr) {
+    const char* who = w ? "mq_group_where_plan" : "mq_group_plan";
     g->tab = static_cast<char*>(pool_alloc(final_bytes(g->range)));
-    if (!g->tab) return set_err(MQ_ENOMEM, "mq_group_plan: table allocation failed");
+    if (!g->tab) return set_err(MQ_ENOMEM, "%s: table allocation failed", who);
     const FinalTab f = final_tab(g->tab, g->range);
     void* scratch = nullptr;
     DenseTabs tabs;
     uint32_t blocks = 0;
     const bool vk = aligned16(keys), vv = aligned16(vals);
-    int rc = vk ? (vv ? launch_dense<true, true>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
+    int rc;
+    if (w)
+        rc = wvec && vk && vv ? launch_where_dense<true>(s, *w, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
+                              : launch_where_dense<false>(s, *w, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st);
+    else
+        rc = vk ? (vv ? launch_dense<true, true>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
                       : launch_dense<true, false>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st))
                 : (vv ? launch_dense<false, true>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
                       : launch_dense<false, false>(s, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st));
+    u64* d_rows = nullptr;
+    if (!rc && rows && !(d_rows = static_cast<u64*>(pool_alloc(sizeof(u64)))))
+        rc = set_err(MQ_ENOMEM, "%s: allocation failed", who);
     if (rc) {
         pool_free_on(scratch, st);
         return rc;
@@ -523,15 +720,21 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
     hipLaunchKernelGGL(k_group_fold, dim3((g->range + kFoldSlots - 1) / kFoldSlots), dim3(kTPB), 0, st, tabs, blocks,
                        g->range, f);
     hipLaunchKernelGGL(k_group_rank, dim3(1), dim3(kTPB), 0, st, f, g->range, tabs.bad, blocks * kWaves);
+    if (d_rows) hipLaunchKernelGGL(k_group_rows, dim3(1), dim3(kTPB), 0, st, f, g->range, d_rows);
     const hipError_t e = hipGetLastError();
     pool_free_on(scratch, st);  // the two kernels queued above are its last readers
-    if (e != hipSuccess) return set_err(MQ_EHIP, "launch of k_group_fold / k_group_rank failed: %s", hipGetErrorString(e));
-    u64 h[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(h, f.hdr, sizeof h, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[1]) return set_err(MQ_EINVAL, "mq_group_plan: %llu keys outside the bounds [%d, %lld]", h[1], g->lo,
+    u64 h[2] = {0, 0}, r = 0;
+    rc = e == hipSuccess ? MQ_OK : set_err(MQ_EHIP, "launch of k_group_fold / k_group_rank failed: %s", hipGetErrorString(e));
+    if (!rc && (hipMemcpyAsync(h, f.hdr, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                (d_rows && hipMemcpyAsync(&r, d_rows, sizeof r, hipMemcpyDeviceToHost, st) != hipSuccess)))
+        rc = set_err(MQ_EHIP, "%s: header download failed", who);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+    pool_free(d_rows);
+    if (rc) return rc;
+    if (h[1]) return set_err(MQ_EINVAL, "%s: %llu keys outside the bounds [%d, %lld]", who, h[1], g->lo,
                              (long long)g->lo + g->range - 1);
     g->groups = h[0];
+    if (rows) *rows = r;
     return MQ_OK;
 }
 
@@ -568,6 +771,7 @@ void release(mq_group* g, hipStream_t st) {
     pool_free_on(g->sorted, st);
     pool_free_on(g->pos, st);
     pool_free_on(g->ccnt, st);
+    pool_free_on(g->own_vals, st);
     delete g;
 }
 
@@ -660,6 +864,138 @@ int mq_group_plan(const int32_t* d_keys, const int32_t* d_vals, uint64_t n, cons
         return rc;
     }
     if (h_path) *h_path = g->path;
+    *h_groups = g->groups;
+    *out = g;
+    return MQ_OK;
+}
+
+int mq_group_where_plan(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* d_keys,
+                        const int32_t* d_vals, uint64_t n, const int32_t* h_key_bounds, int path, mq_group** out,
+                        uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream) {
+    const char* who = "mq_group_where_plan";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (out) *out = nullptr;
+    if (h_groups) *h_groups = 0;
+    if (h_rows) *h_rows = 0;
+    if (!out || !h_groups || !d_cols || !h_ranges) return set_err(MQ_EINVAL, "%s: NULL pointer", who);
+    if (ncols < 1 || ncols > MQ_WHERE_MAX_COLS)
+        return set_err(MQ_EINVAL, "%s: ncols %d outside 1..%d", who, ncols, (int)MQ_WHERE_MAX_COLS);
+    if (path != MQ_GROUP_AUTO && path != MQ_GROUP_DENSE && path != MQ_GROUP_SORT)
+        return set_err(MQ_EINVAL, "%s: path %d", who, path);
+    if (n >= (1ull << 31)) return set_err(MQ_EINVAL, "%s: n >= 2^31", who);
+    if (n) {
+        for (int c = 0; c < ncols; c++)
+            if (!d_cols[c] || (reinterpret_cast<uintptr_t>(d_cols[c]) & 3u))
+                return set_err(MQ_EINVAL, "%s: column %d NULL or not 4-byte aligned", who, c);
+        if (!d_keys || !d_vals || (reinterpret_cast<uintptr_t>(d_keys) & 3u) || (reinterpret_cast<uintptr_t>(d_vals) & 3u))
+            return set_err(MQ_EINVAL, "%s: key or value column NULL or not 4-byte aligned", who);
+        if (h_key_bounds && h_key_bounds[0] > h_key_bounds[1])
+            return set_err(MQ_EINVAL, "%s: bounds [%d, %d] are empty", who, h_key_bounds[0], h_key_bounds[1]);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    WhereArgs a;
+    bool empty, vec;
+    fold_ranges(d_cols, h_ranges, ncols, &a, &empty, &vec);
+    mq_group* g = new (std::nothrow) mq_group();
+    if (!g) return set_err(MQ_ENOMEM, "%s: out of host memory", who);
+    g->dev = dev;
+    g->n = n;
+    g->vals = d_vals;
+    g->stream = st;
+    g->path = path == MQ_GROUP_SORT ? MQ_GROUP_SORT : MQ_GROUP_DENSE;  // what a plan without rows reports
+    auto no_groups = [&]() {
+        if (h_path) *h_path = g->path;
+        *out = g;
+        return MQ_OK;
+    };
+    if (n == 0 || empty) return no_groups();
+
+    // The workspace of mq_where_agg (the bounds) and of mq_where_positions (the sort path).
+    void* ws = nullptr;
+    const size_t ws_bytes = mq_where_workspace_bytes(n);
+    auto fail = [&](int code) {
+        pool_free_on(ws, st);
+        release(g, st);
+        return code;
+    };
+    int32_t lo, hi;
+    uint64_t rows = 0;
+    bool rows_known = false;
+    if (h_key_bounds) {
+        lo = h_key_bounds[0];
+        hi = h_key_bounds[1];
+    } else {  // one more pass over the predicates and the key lines that hold a survivor
+        ws = pool_alloc(ws_bytes);
+        mq_agg* d_agg = static_cast<mq_agg*>(pool_alloc(sizeof(mq_agg)));
+        mq_agg ag = {};
+        rc = ws && d_agg ? MQ_OK : set_err(MQ_ENOMEM, "%s: workspace allocation failed", who);
+        if (!rc) rc = mq_where_agg(d_cols, h_ranges, ncols, d_keys, n, d_agg, ws, ws_bytes, stream);
+        if (!rc && hipMemcpyAsync(&ag, d_agg, sizeof ag, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "%s: bounds download failed", who);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+        pool_free(d_agg);
+        if (rc) return fail(rc);
+        if (ag.count == 0) {
+            pool_free(ws);
+            return no_groups();
+        }
+        lo = ag.min;
+        hi = ag.max;
+        rows = ag.count;
+        rows_known = true;
+    }
+    const int64_t range = (int64_t)hi - (int64_t)lo + 1;  // up to 2^32
+    if (path == MQ_GROUP_DENSE && range > (int64_t)kDenseSlots)
+        return fail(set_err(MQ_EINVAL, "%s: key range %lld exceeds the dense path's %u slots", who, (long long)range,
+                            kDenseSlots));
+    g->path = path != MQ_GROUP_AUTO ? path : range <= (int64_t)kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
+    if (g->path == MQ_GROUP_DENSE) {
+        pool_free(ws);  // idle: mq_where_agg's stream has been waited for
+        ws = nullptr;
+        g->lo = lo;
+        g->range = (uint32_t)range;
+        rc = plan_dense(s, g, d_keys, d_vals, n, st, &a, vec, rows_known || !h_rows ? nullptr : &rows);
+        if (rc) return fail(rc);
+    } else {
+        // the K matching rows' positions, then their keys and values, then the sort path on those
+        if (!ws) ws = pool_alloc(ws_bytes);
+        int32_t* pos = static_cast<int32_t*>(pool_alloc(n * 4));
+        u64* d_k = static_cast<u64*>(pool_alloc(sizeof(u64)));
+        u64 k = 0;
+        rc = ws && pos && d_k ? MQ_OK : set_err(MQ_ENOMEM, "%s: allocation failed", who);
+        if (!rc)
+            rc = mq_where_positions(d_cols, h_ranges, ncols, nullptr, n, pos, reinterpret_cast<uint64_t*>(d_k), ws, ws_bytes,
+                                    stream);
+        if (!rc && hipMemcpyAsync(&k, d_k, sizeof k, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "%s: count download failed", who);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+        pool_free(d_k);
+        pool_free(ws);
+        ws = nullptr;
+        int32_t* ck = nullptr;
+        if (!rc && k) {
+            ck = static_cast<int32_t*>(pool_alloc(k * 4));
+            g->own_vals = static_cast<int32_t*>(pool_alloc(k * 4));
+            if (!ck || !g->own_vals) rc = set_err(MQ_ENOMEM, "%s: allocation failed", who);
+            if (!rc) rc = mq_fetch(d_keys, pos, k, ck, stream);
+            if (!rc) rc = mq_fetch(d_vals, pos, k, g->own_vals, stream);
+        }
+        pool_free_on(pos, st);  // the gathers queued above are its last readers
+        if (!rc && k) {
+            g->vals = g->own_vals;
+            g->n = k;
+            rc = plan_sort(g, ck, k, h_key_bounds, st);  // synchronises
+        }
+        pool_free_on(ck, st);
+        if (rc) return fail(rc);
+        rows = k;
+    }
+    if (h_path) *h_path = g->path;
+    if (h_rows) *h_rows = rows;
     *h_groups = g->groups;
     *out = g;
     return MQ_OK;

@@ -1089,30 +1089,10 @@ static Result* long_result_from_device(const void* d_src, size_t n, Status* st) 
     return new_result(LONG, n, host);
 }
 
-/* Grouped count / sum / min / max of `values` by `keys` (no reference counterpart;
- * DESIGN.md §3.11): five Results of one entry per distinct key, in ascending key order:
- * keys (INT), count (LONG), sum (LONG), min (INT), max (INT). */
-Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Status* ret_status) {
-    if (op_begin(ret_status)) return NULL;
-    const int32_t *dk = NULL, *dv = NULL;
-    size_t n = 0, nv = 0;
-    int bad = !keys || !values;
-    if (!bad) {
-        const int a = gcol_device(keys, &dk, &n, ret_status);
-        if (a > 0) return NULL;
-        const int b = a ? a : gcol_device(values, &dv, &nv, ret_status);
-        if (b > 0) return NULL;
-        bad = a < 0 || b < 0;
-    }
-    if (bad || n != nv) {
-        dml_fail(ret_status, "group_aggregate",
-                 bad ? "keys and values must each be a Column or an INT Result" : "keys and values differ in length");
-        return NULL;
-    }
-    mq_group* g = NULL;
-    uint64_t groups = 0;
+/* The five Results of a planned group handle, which is freed here: keys (INT), count (LONG),
+ * sum (LONG), min (INT), max (INT), one entry per group. rc: the plan's return code. */
+static Result** group_results(const char* who, mq_group* g, uint64_t groups, int rc, Status* ret_status) {
     void* buf = NULL;
-    int rc = mq_group_plan(dk, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, g_stream);
     /* one block: count and sum (8 bytes an entry) first, then keys, min and max */
     if (!rc) rc = dev_alloc(&buf, groups ? (size_t)groups * 28 : 16);
     uint64_t* d_count = (uint64_t*)buf;
@@ -1124,7 +1104,7 @@ Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Sta
     if (rc) {
         mq_stream_sync(g_stream);
         mq_pool_free(buf);
-        fail(ret_status, "group_aggregate", rc);
+        fail(ret_status, who, rc);
         return NULL;
     }
     Result** out = (Result**)calloc(5, sizeof(Result*));
@@ -1148,6 +1128,32 @@ Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Sta
         }
     ret_status->code = OK;
     return out;
+}
+
+/* Grouped count / sum / min / max of `values` by `keys` (no reference counterpart;
+ * DESIGN.md §3.11): five Results of one entry per distinct key, in ascending key order:
+ * keys (INT), count (LONG), sum (LONG), min (INT), max (INT). */
+Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const int32_t *dk = NULL, *dv = NULL;
+    size_t n = 0, nv = 0;
+    int bad = !keys || !values;
+    if (!bad) {
+        const int a = gcol_device(keys, &dk, &n, ret_status);
+        if (a > 0) return NULL;
+        const int b = a ? a : gcol_device(values, &dv, &nv, ret_status);
+        if (b > 0) return NULL;
+        bad = a < 0 || b < 0;
+    }
+    if (bad || n != nv) {
+        dml_fail(ret_status, "group_aggregate",
+                 bad ? "keys and values must each be a Column or an INT Result" : "keys and values differ in length");
+        return NULL;
+    }
+    mq_group* g = NULL;
+    uint64_t groups = 0;
+    const int rc = mq_group_plan(dk, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, g_stream);
+    return group_results("group_aggregate", g, groups, rc, ret_status);
 }
 
 /* The first min(k, rows) entries of `values` in ascending or descending order, equal values
@@ -1302,6 +1308,32 @@ Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, i
     out[3] = new_result(INT, 1, mx);
     ret_status->code = OK;
     return out;
+}
+
+/* group_aggregate over the rows for which every range holds (no reference counterpart;
+ * DESIGN.md §3.14): what select_where -> fetch_column x 2 -> group_aggregate returns, in one
+ * operator. No key bounds are passed (group_aggregate's reason): the plan finds the range of
+ * the matching keys itself. */
+Result** group_aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn* keys,
+                               GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t *dk = NULL, *dv = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0, nv = 0;
+    const char* who = "group_aggregate_where";
+    if (where_args(who, columns, lows, highs, ncols, keys, d_cols, ranges, &dk, &n, ret_status)) return NULL;
+    const int b = values ? gcol_device(values, &dv, &nv, ret_status) : -1;
+    if (b > 0) return NULL;
+    if (b < 0 || nv != n) {
+        dml_fail(ret_status, who, b < 0 ? "values must be a Column or an INT Result" : "the columns and values differ in length");
+        return NULL;
+    }
+    mq_group* g = NULL;
+    uint64_t groups = 0;
+    const int rc = mq_group_where_plan(d_cols, ranges, ncols, dk, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, NULL,
+                                       g_stream);
+    return group_results(who, g, groups, rc, ret_status);
 }
 
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner

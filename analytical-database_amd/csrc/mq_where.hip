@@ -43,6 +43,7 @@
 #include "mq_common.h"
 #include "mq_device.h"
 #include "mq_scan_common.h"
+#include "mq_where_common.h"
 
 namespace {
 
@@ -53,72 +54,6 @@ constexpr int kWhU = 8;                        // tiles in flight per lane
 constexpr int kWaveRows = 256;                 // rows of a wave tile
 constexpr int kExpTile = 4096;                 // rows per expand block
 constexpr int kExpWt = kExpTile / kWaveRows;   // its wave tiles
-
-struct WhereArgs {
-    const int32_t* col[MQ_WHERE_MAX_COLS];
-    uint32_t lo[MQ_WHERE_MAX_COLS];   // Pred's fold: v matches when (uint32)(v - lo) <= wm1
-    uint32_t wm1[MQ_WHERE_MAX_COLS];
-    int ncols;                        // predicates that read a column: 0 .. MQ_WHERE_MAX_COLS
-};
-
-// The lane's four rows as a nibble: bit e set when row e is in range.
-__device__ __forceinline__ uint32_t match4(int4 v, uint32_t lo, uint32_t wm1) {
-    return (uint32_t)((uint32_t)v.x - lo <= wm1) | ((uint32_t)((uint32_t)v.y - lo <= wm1) << 1) |
-           ((uint32_t)((uint32_t)v.z - lo <= wm1) << 2) | ((uint32_t)((uint32_t)v.w - lo <= wm1) << 3);
-}
-
-// Whether one of the 8 lanes that share this lane's 128-byte line is set in the ballot.
-__device__ __forceinline__ bool line_live(u64 ballot, int lane) { return ((ballot >> (lane & 56)) & 0xffull) != 0; }
-
-// live[u] = the surviving rows of U full tiles (lane's rows `row` + u * kTileRows .. + 3).
-template <bool VEC, int U>
-__device__ __forceinline__ void live_tiles(const WhereArgs& a, uint64_t row, int lane, uint32_t (&live)[U]) {
-    if (a.ncols == 0) {  // every range matches everything
-#pragma unroll
-        for (int u = 0; u < U; u++) live[u] = 15u;
-        return;
-    }
-    int4 v[U];
-    {
-        const int32_t* __restrict__ p = a.col[0] + row;
-#pragma unroll
-        for (int u = 0; u < U; u++) v[u] = load4_nt<VEC>(p + (uint64_t)u * kTileRows);
-        const uint32_t lo = a.lo[0], wm1 = a.wm1[0];
-#pragma unroll
-        for (int u = 0; u < U; u++) live[u] = match4(v[u], lo, wm1);
-    }
-    for (int c = 1; c < a.ncols; c++) {
-        u64 b[U];
-        u64 any = 0;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            b[u] = __ballot(live[u] != 0u);
-            any |= b[u];
-        }
-        if (any == 0) break;  // wave-uniform: nothing left in the iteration
-        const int32_t* __restrict__ p = a.col[c] + row;
-#pragma unroll
-        for (int u = 0; u < U; u++)
-            if (b[u] != 0 && line_live(b[u], lane)) v[u] = load4_nt<VEC>(p + (uint64_t)u * kTileRows);
-        const uint32_t lo = a.lo[c], wm1 = a.wm1[c];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-            if (b[u] != 0 && line_live(b[u], lane)) live[u] &= match4(v[u], lo, wm1);
-    }
-}
-
-// The column's last, ragged tile: row by row, no row at or past `end` from any column.
-__device__ __forceinline__ uint32_t live_ragged(const WhereArgs& a, uint64_t row, uint64_t end) {
-    uint32_t live = 0;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        if (row + e >= end) continue;
-        bool ok = true;
-        for (int c = 0; c < a.ncols && ok; c++) ok = (uint32_t)a.col[c][row + e] - a.lo[c] <= a.wm1[c];
-        live |= (uint32_t)ok << e;
-    }
-    return live;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kTPB, 8) void k_where_mask(WhereArgs a, uint64_t n, uint64_t rows_per_block,
@@ -336,22 +271,7 @@ int prepare(const char* who, const int32_t* const* d_cols, const mq_range* h_ran
     }
     if (!d_ws || ws_bytes < layout(n).total || (reinterpret_cast<uintptr_t>(d_ws) & 15u))
         return set_err(MQ_EINVAL, "%s: workspace NULL, short or not 16-byte aligned", who);
-    *a = WhereArgs{};
-    *empty = false;
-    *vec = true;
-    for (int c = 0; c < ncols; c++) {
-        Pred p;
-        if (!make_pred(h_ranges[c].has_low, h_ranges[c].low, h_ranges[c].has_high, h_ranges[c].high, &p)) {
-            *empty = true;
-            return MQ_OK;
-        }
-        if (p.wm1 == 0xFFFFFFFFu) continue;  // matches every int32: the column is not read
-        a->col[a->ncols] = d_cols[c];
-        a->lo[a->ncols] = p.lo;
-        a->wm1[a->ncols] = p.wm1;
-        a->ncols++;
-        *vec = *vec && aligned16(d_cols[c]);
-    }
+    fold_ranges(d_cols, h_ranges, ncols, a, empty, vec);
     return MQ_OK;
 }
 

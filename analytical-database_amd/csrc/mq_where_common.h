@@ -1,0 +1,108 @@
+// mq_where_common.h — internal (not exported) pieces shared by the kernels that stream
+// under a conjunction of range predicates (mq_where.hip, k_group_where_dense in
+// mq_group.hip): the folded predicates as kernel arguments, a lane's surviving rows per
+// tile with the dead 128-byte lines of the later columns skipped, and the host's fold.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "mq_common.h"
+#include "mq_device.h"
+#include "mq_scan_common.h"
+
+namespace mqi {
+
+struct WhereArgs {
+    const int32_t* col[MQ_WHERE_MAX_COLS];
+    uint32_t lo[MQ_WHERE_MAX_COLS];   // Pred's fold: v matches when (uint32)(v - lo) <= wm1
+    uint32_t wm1[MQ_WHERE_MAX_COLS];
+    int ncols;                        // predicates that read a column: 0 .. MQ_WHERE_MAX_COLS
+};
+
+// The lane's four rows as a nibble: bit e set when row e is in range.
+__device__ __forceinline__ uint32_t match4(int4 v, uint32_t lo, uint32_t wm1) {
+    return (uint32_t)((uint32_t)v.x - lo <= wm1) | ((uint32_t)((uint32_t)v.y - lo <= wm1) << 1) |
+           ((uint32_t)((uint32_t)v.z - lo <= wm1) << 2) | ((uint32_t)((uint32_t)v.w - lo <= wm1) << 3);
+}
+
+// Whether one of the 8 lanes that share this lane's 128-byte line is set in the ballot.
+__device__ __forceinline__ bool line_live(unsigned long long ballot, int lane) {
+    return ((ballot >> (lane & 56)) & 0xffull) != 0;
+}
+
+// live[u] = the surviving rows of U full tiles (lane's rows `row` + u * kTileRows .. + 3).
+template <bool VEC, int U>
+__device__ __forceinline__ void live_tiles(const WhereArgs& a, uint64_t row, int lane, uint32_t (&live)[U]) {
+    if (a.ncols == 0) {  // every range matches everything
+#pragma unroll
+        for (int u = 0; u < U; u++) live[u] = 15u;
+        return;
+    }
+    int4 v[U];
+    {
+        const int32_t* __restrict__ p = a.col[0] + row;
+#pragma unroll
+        for (int u = 0; u < U; u++) v[u] = load4_nt<VEC>(p + (uint64_t)u * kTileRows);
+        const uint32_t lo = a.lo[0], wm1 = a.wm1[0];
+#pragma unroll
+        for (int u = 0; u < U; u++) live[u] = match4(v[u], lo, wm1);
+    }
+    for (int c = 1; c < a.ncols; c++) {
+        unsigned long long b[U];
+        unsigned long long any = 0;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            b[u] = __ballot(live[u] != 0u);
+            any |= b[u];
+        }
+        if (any == 0) break;  // wave-uniform: nothing left in the iteration
+        const int32_t* __restrict__ p = a.col[c] + row;
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (b[u] != 0 && line_live(b[u], lane)) v[u] = load4_nt<VEC>(p + (uint64_t)u * kTileRows);
+        const uint32_t lo = a.lo[c], wm1 = a.wm1[c];
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (b[u] != 0 && line_live(b[u], lane)) live[u] &= match4(v[u], lo, wm1);
+    }
+}
+
+// The column's last, ragged tile: row by row, no row at or past `end` from any column.
+__device__ __forceinline__ uint32_t live_ragged(const WhereArgs& a, uint64_t row, uint64_t end) {
+    uint32_t live = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        if (row + e >= end) continue;
+        bool ok = true;
+        for (int c = 0; c < a.ncols && ok; c++) ok = (uint32_t)a.col[c][row + e] - a.lo[c] <= a.wm1[c];
+        live |= (uint32_t)ok << e;
+    }
+    return live;
+}
+
+// The host's fold of ncols checked (column, range) pairs into *a. A range that matches
+// every int32 drops out (its column is not read). *empty: some range matches no int32 (*a
+// is then incomplete); *vec: every column that is read lies on a 16-byte boundary.
+inline void fold_ranges(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, WhereArgs* a, bool* empty,
+                        bool* vec) {
+    *a = WhereArgs{};
+    *empty = false;
+    *vec = true;
+    for (int c = 0; c < ncols; c++) {
+        Pred p;
+        if (!make_pred(h_ranges[c].has_low, h_ranges[c].low, h_ranges[c].has_high, h_ranges[c].high, &p)) {
+            *empty = true;
+            return;
+        }
+        if (p.wm1 == 0xFFFFFFFFu) continue;  // matches every int32: the column is not read
+        a->col[a->ncols] = d_cols[c];
+        a->lo[a->ncols] = p.lo;
+        a->wm1[a->ncols] = p.wm1;
+        a->ncols++;
+        *vec = *vec && aligned16(d_cols[c]);
+    }
+}
+
+}  // namespace mqi

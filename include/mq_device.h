@@ -394,6 +394,52 @@ int mq_group_write(mq_group* g, int32_t* d_keys_out, uint64_t* d_count_out,
                    void* stream);
 int mq_group_free(mq_group* g);
 
+/* ---- GROUP BY under a WHERE, in one pass ----
+ * mq_group_plan over the rows for which a conjunction of range predicates holds: with
+ * m[i] = every range holds for row i (d_cols, h_ranges and ncols as mq_where_positions takes
+ * and defines them, further down in this header; the predicates are evaluated in the order
+ * given, the most selective belongs first), the result is exactly that of mq_group_plan over
+ * (d_keys[m], d_vals[m]): one entry per distinct key with a matching row, ascending, u64
+ * count, exact int64 sum, min and max; bitwise the same whatever the path, the grid, the
+ * order of the predicates or the alignment. The handle is an ordinary mq_group, served by
+ * mq_group_write and mq_group_free. *h_rows (may be NULL) = the matching rows, the sum of the
+ * counts. d_keys and d_vals may be each other or any predicate column.
+ * h_key_bounds (NULL or a host {lo, hi}, inclusive) constrains the keys of MATCHING rows
+ *        only: the key of a row that fails a predicate is never an error and never an
+ *        address. NULL costs one more pass over the predicates and over the key lines that
+ *        hold a survivor (mq_where_agg on the key column), which finds the range of the
+ *        matching keys alone: a filter that narrows the keys to mq_group_dense_slots() values
+ *        lands on the dense path whatever the column holds elsewhere. The range hi - lo + 1
+ *        picks the path as in mq_group_plan; `path` forces one.
+ * dense: one streaming pass, k_group_where_dense: the predicate columns as mq_where_agg
+ *        reads them, then of the key and the value column only the 128-byte lines in which a
+ *        row survived, into the per-block LDS tables of mq_group_plan's dense path.
+ * sort:  mq_where_positions, the K matching rows' keys and values gathered (mq_fetch) into
+ *        two buffers the handle owns or frees, then mq_group_plan's sort path on those; given
+ *        bounds are checked against the sorted ends.
+ * Measured at 1e9 rows against mq_where_positions -> mq_fetch x 2 ->
+ * mq_group_plan with the same bounds: with bounds given 0.59-0.68 of the chain's time when
+ * 10 % of the rows match and 0.24-0.41 at 100 %, a win at 0.1-1 % too behind a uniform leading
+ * column but a loss there behind a clustered one (1.07-1.56; a few blocks do every table
+ * update); with NULL bounds a win from 50 % upward (0.37-0.88), a tie at 10 % and a loss below
+ * (1.2-2.3). Every range unbounded runs 3-5 % behind mq_group_plan. Nothing is dispatched
+ * differently by selectivity.
+ * Synchronises; takes its scratch from the library's pool. n == 0, a range that no int32
+ * satisfies (no column is read) or no matching row give MQ_OK, zero groups and a handle to
+ * free. d_vals must stay valid until the write has run (dense path).
+ * MQ_EINVAL, with *out = NULL, *h_groups = 0 and nothing allocated: ncols outside 1..8,
+ * n >= 2^31, a NULL d_cols, h_ranges, out or h_groups, a NULL or not 4-byte aligned column,
+ * key or value pointer with n > 0, a path that is none of the three, lo > hi with n > 0; and
+ * with everything released: a matching row whose key lies outside the given bounds,
+ * MQ_GROUP_DENSE forced on a wider range. */
+struct mq_range;
+int mq_group_where_plan(const int32_t* const* d_cols /* host array of ncols device pointers */,
+                        const struct mq_range* h_ranges, int ncols, const int32_t* d_keys,
+                        const int32_t* d_vals, uint64_t n,
+                        const int32_t* h_key_bounds /* NULL or {lo, hi} inclusive */, int path,
+                        mq_group** out, uint64_t* h_groups, int* h_path /* may be NULL */,
+                        uint64_t* h_rows /* matching rows; may be NULL */, void* stream);
+
 /* ---- top k: the k smallest or largest rows, in order ----
  * n < 2^31 int32 values d_vals[i] with an optional int32 payload d_payload[i] (a positions
  * vector, the pair select_result takes; NULL: the payload is the row id i). The output is

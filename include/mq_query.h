@@ -326,6 +326,28 @@ Result* select_where(GeneralizedColumn** columns, int** lows, int** highs, int n
 Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
                          GeneralizedColumn* values, Status* ret_status);
 
+/* ---- GROUP BY under a WHERE (not in the reference) ----
+ * group_aggregate_where: SELECT key, count(*), sum(v), min(v), max(v) FROM t WHERE c0 IN [..)
+ * AND c1 IN [..) ... GROUP BY key in one operator (mq_group_where_plan in
+ * mq_device.h): what select_where -> fetch_column x 2 -> group_aggregate returns, without the
+ * positions, the two fetched columns and the host round trip between them. `columns`, `lows`,
+ * `highs` and `ncols` are select_where's, `keys` and `values` group_aggregate's: each a COLUMN
+ * or an INT RESULT, all equally long; keys, values and any predicate column may be the same
+ * object. Returns group_aggregate's five Results under the same ownership and shadow rules:
+ * one tuple per distinct key that has a matching row, ascending: [0] keys (INT), [1] counts
+ * (LONG), [2] sums (LONG), [3] minima (INT), [4] maxima (INT). No matching row gives five
+ * empty Results and OK. No key bounds are passed, for group_aggregate's reason: the range of
+ * the matching keys is found in one more pass over the predicates and the surviving key
+ * lines, so a filter that narrows the keys to mq_group_dense_slots() values takes the dense
+ * path. Measured on the device at 1e9 rows, the plan as called here (no
+ * bounds) beats mq_where_positions -> mq_fetch x 2 -> mq_group_plan when half of the rows or
+ * more match, ties at 10 % and loses below. Put the most selective predicate first. The operator runs on the calling device: a
+ * column held as row shards drops them and is split again on next use. ERROR and NULL (a
+ * "libmq:" line on stderr): no device, ncols outside 1..8, an argument of the wrong kind,
+ * different lengths, 2^31 rows or more, a device failure. */
+Result** group_aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
+                               GeneralizedColumn* keys, GeneralizedColumn* values, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
