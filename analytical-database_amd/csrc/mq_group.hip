@@ -50,6 +50,24 @@
 //   sort path          : mq_where_positions, the keys and the values of the K matching rows
 //                        gathered with mq_fetch into two buffers, then the sort path above
 //                        on them; the handle owns the gathered values.
+//
+// mq_group_by_plan groups by a tuple of two to four key columns, in
+// lexicographic order, on the same handle. With per-column bounds [lo_j, hi_j], ranges
+// range_j = hi_j - lo_j + 1 and strides stride_last = 1, stride_j = stride_{j+1} * range_{j+1},
+// a tuple's code sum((K_j - lo_j) * stride_j) orders as the tuples do; the key space P =
+// prod(range_j) picks the path. Every component is checked against its own range: a stray
+// component can leave the summed code inside [0, P).
+//   k_group_by_dense   : (P <= kDenseSlots) k_group_dense's stream over the nkeys + 1 columns,
+//                        the code as the slot; a row out of bounds takes slot ~0, which no
+//                        table holds, and is counted. The run fold keeps tiles whose 256
+//                        slots are equal. Fold, rank and write kernels serve unchanged.
+//   k_group_by_pack    : (P <= 2^32) reads the key columns once and writes the int32 column
+//                        code ^ 0x80000000, whose signed order is the tuples' order; rows out
+//                        of bounds are counted per wave (k_group_by_bad sums them). The sort
+//                        path above then runs on that column.
+//   k_group_by_unpack  : the write kernels put each group's slot or code into a temporary;
+//                        this decodes it into the key outputs, K_j = lo_j + (code / stride_j)
+//                        % range_j.
 
 #include <hip/hip_runtime.h>
 
@@ -80,6 +98,12 @@ struct mq_group {
     uint32_t* ccnt;
     uint32_t blocks;
     uint64_t chunk;
+    // mq_group_by_plan with nkeys > 1 (0 otherwise): the tuple behind a slot (dense, lo = 0) or
+    // behind a sorted code, K_j = klo[j] + (code / kstride[j]) % (krm1[j] + 1)
+    int nkeys;
+    int32_t klo[MQ_GROUP_MAX_KEYS];
+    uint32_t krm1[MQ_GROUP_MAX_KEYS];
+    uint32_t kstride[MQ_GROUP_MAX_KEYS];
 };
 
 namespace {
@@ -488,6 +512,271 @@ __global__ __launch_bounds__(kTPB) void k_group_dense_write(FinalTab f, uint32_t
     if (max_out) max_out[o] = f.mx[s];
 }
 
+// ---- grouping by a tuple of key columns (mq_group_by_plan) ----
+
+constexpr int kMaxKeys = MQ_GROUP_MAX_KEYS;
+constexpr uint32_t kNoSlot = ~0u;  // of a row with a component out of bounds: beyond every table
+
+// Tiles of each column in flight per thread: (nkeys + 1) * by_tiles(nkeys) dwordx4 of loaded
+// data a lane, 192 B with two and three key columns and 160 B with four.
+constexpr int by_tiles(int nkeys) { return nkeys == 2 ? 4 : nkeys == 3 ? 3 : 2; }
+
+struct ByArgs {
+    const int* keys[kMaxKeys];
+    uint32_t lo[kMaxKeys];
+    uint32_t rm1[kMaxKeys];     // range - 1: a range of 2^32 has no u32
+    uint32_t stride[kMaxKeys];  // mod 2^32: a stride of 2^32 (held as 0) only meets K_j - lo_j = 0
+};
+
+struct ByKeysOut {
+    int32_t* keys[kMaxKeys];
+};
+
+// The code of one row's tuple; *in: every component lies within its own column's bounds. A
+// check of the sum would not do: (3, 12) under ranges (10, 10) sums to 42, inside the table.
+template <int NK>
+__device__ __forceinline__ uint32_t row_code(const ByArgs& a, const int (&k)[NK], bool* in) {
+    uint32_t c = 0;
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < NK; j++) {
+        const uint32_t d = (uint32_t)k[j] - a.lo[j];  // a key below lo wraps past the range
+        ok = ok && d <= a.rm1[j];
+        c += d * a.stride[j];
+    }
+    *in = ok;
+    return c;
+}
+
+__device__ __forceinline__ int elem(const int4& q, int e) { return e == 0 ? q.x : e == 1 ? q.y : e == 2 ? q.z : q.w; }
+
+// The codes of a lane's four rows of one tile; bit e of *in: row e is within the bounds.
+template <int NK>
+__device__ __forceinline__ uint4 tile_codes(const ByArgs& a, const int4 (&k)[NK], uint32_t* in) {
+    uint32_t c[4], m = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        int r[NK];
+#pragma unroll
+        for (int j = 0; j < NK; j++) r[j] = elem(k[j], e);
+        bool ok;
+        c[e] = row_code<NK>(a, r, &ok);
+        m |= ok ? 1u << e : 0u;
+    }
+    *in = m;
+    return make_uint4(c[0], c[1], c[2], c[3]);
+}
+
+// k_group_dense over NK key columns: the slot is the tuple's code (range = the key space, at
+// most kDenseSlots), kNoSlot for a row out of bounds, so that a tile of 256 equal tuples is a
+// tile of 256 equal slots and the run fold works on slots.
+template <int NK, bool VEC>
+__global__ __launch_bounds__(kTPB, 4) void k_group_by_dense(ByArgs a, const int* vals, uint64_t n, uint64_t rows_per_block,
+                                                            uint32_t range, DenseTabs out) {
+    constexpr int U = by_tiles(NK);
+    __shared__ uint32_t s_cnt[kDenseSlots];
+    __shared__ u64 s_sum[kDenseSlots];
+    __shared__ int s_mn[kDenseSlots];
+    __shared__ int s_mx[kDenseSlots];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        s_cnt[s] = 0u;
+        s_sum[s] = 0ull;
+        s_mn[s] = INT_MAX;
+        s_mx[s] = INT_MIN;
+    }
+    __syncthreads();
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    uint32_t nbad = 0;
+    // the wave's run of tiles whose 256 slots all equal run_slot, folded per lane
+    uint32_t run_slot = 0;
+    uint32_t run_tiles = 0;
+    long long r_sum = 0;
+    int r_mn = INT_MAX, r_mx = INT_MIN;
+
+    auto update = [&](uint32_t s, int v) {
+        if (s < range) {  // kNoSlot never is
+            atomicAdd(&s_cnt[s], 1u);
+            atomicAdd(&s_sum[s], (u64)(long long)v);
+            atomicMin(&s_mn[s], v);
+            atomicMax(&s_mx[s], v);
+        } else {
+            nbad++;
+        }
+    };
+    auto flush = [&]() {  // wave-uniform
+        const long long sm = wave_sum_i64(r_sum);
+        const int mn = wave_min(r_mn), mx = wave_max(r_mx);
+        if (lane == 0) {
+            if (run_slot < range) {
+                atomicAdd(&s_cnt[run_slot], run_tiles * 256u);
+                atomicAdd(&s_sum[run_slot], (u64)sm);
+                atomicMin(&s_mn[run_slot], mn);
+                atomicMax(&s_mx[run_slot], mx);
+            } else {
+                nbad += run_tiles * 256u;
+            }
+        }
+        run_tiles = 0;
+        r_sum = 0;
+        r_mn = INT_MAX;
+        r_mx = INT_MIN;
+    };
+    auto consume = [&](const int4 (&k)[NK], int4 v) {  // a full tile
+        uint32_t in;
+        const uint4 c = tile_codes<NK>(a, k, &in);
+        const uint32_t sx = in & 1u ? c.x : kNoSlot, sy = in & 2u ? c.y : kNoSlot, sz = in & 4u ? c.z : kNoSlot,
+                       sw = in & 8u ? c.w : kNoSlot;
+        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)sx);
+        if (__all(sx == s0 && sy == s0 && sz == s0 && sw == s0)) {
+            if (run_tiles && s0 != run_slot) flush();
+            run_slot = s0;
+            run_tiles++;
+            r_sum += (long long)v.x + (long long)v.y + (long long)v.z + (long long)v.w;
+            r_mn = min(r_mn, min(min(v.x, v.y), min(v.z, v.w)));
+            r_mx = max(r_mx, max(max(v.x, v.y), max(v.z, v.w)));
+        } else {
+            update(sx, v.x);
+            update(sy, v.y);
+            update(sz, v.z);
+            update(sw, v.w);
+        }
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)U * kTileRows <= end; t += (uint64_t)U * kTileRows) {
+        int4 k[U][NK], v[U];
+#pragma unroll
+        for (int j = 0; j < NK; j++)
+#pragma unroll
+            for (int u = 0; u < U; u++) k[u][j] = load4_nt<VEC>(a.keys[j] + t + (uint64_t)u * kTileRows + (uint64_t)tid * 4);
+#pragma unroll
+        for (int u = 0; u < U; u++) v[u] = load4_nt<VEC>(vals + t + (uint64_t)u * kTileRows + (uint64_t)tid * 4);
+#pragma unroll
+        for (int u = 0; u < U; u++) consume(k[u], v[u]);
+    }
+    for (; t < end; t += kTileRows) {  // the chunk's tail
+        const uint64_t row = t + (uint64_t)tid * 4;
+        if (t + kTileRows <= end) {    // block-uniform
+            int4 k[NK];
+#pragma unroll
+            for (int j = 0; j < NK; j++) k[j] = load4_nt<VEC>(a.keys[j] + row);
+            consume(k, load4_nt<VEC>(vals + row));
+        } else {                       // the last ragged tile: row by row, none past the end
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (row + e < end) {
+                    int r[NK];
+#pragma unroll
+                    for (int j = 0; j < NK; j++) r[j] = a.keys[j][row + e];
+                    bool ok;
+                    const uint32_t c = row_code<NK>(a, r, &ok);
+                    update(ok ? c : kNoSlot, vals[row + e]);
+                }
+        }
+    }
+    if (run_tiles) flush();
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) out.bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * range;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        out.cnt[base + s] = s_cnt[s];
+        out.sum[base + s] = (long long)s_sum[s];
+        out.mn[base + s] = s_mn[s];
+        out.mx[base + s] = s_mx[s];
+    }
+}
+
+// out[i] = code(row i) ^ 0x80000000 over n rows, k_group_dense's chunking; bad[block][wave] =
+// the rows with a component out of bounds (their out entry means nothing: the plan fails).
+// out is 16-byte aligned (a pool block), so a lane's four codes leave as one dwordx4.
+template <int NK, bool VEC>
+__global__ __launch_bounds__(kTPB) void k_group_by_pack(ByArgs a, uint64_t n, uint64_t rows_per_block, int32_t* __restrict__ out,
+                                                        uint32_t* __restrict__ bad) {
+    constexpr int U = by_tiles(NK);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+    uint32_t nbad = 0;
+    auto pack = [&](const int4 (&k)[NK], uint64_t row) {  // a full tile; row < end, a multiple of 4
+        uint32_t in;
+        const uint4 c = tile_codes<NK>(a, k, &in);
+        nbad += 4u - (uint32_t)__popc(in);
+        *reinterpret_cast<int4*>(out + row) = make_int4((int)(c.x ^ 0x80000000u), (int)(c.y ^ 0x80000000u),
+                                                        (int)(c.z ^ 0x80000000u), (int)(c.w ^ 0x80000000u));
+    };
+    uint64_t t = start;
+    for (; t + (uint64_t)U * kTileRows <= end; t += (uint64_t)U * kTileRows) {
+        int4 k[U][NK];
+#pragma unroll
+        for (int j = 0; j < NK; j++)
+#pragma unroll
+            for (int u = 0; u < U; u++) k[u][j] = load4_nt<VEC>(a.keys[j] + t + (uint64_t)u * kTileRows + (uint64_t)tid * 4);
+#pragma unroll
+        for (int u = 0; u < U; u++) pack(k[u], t + (uint64_t)u * kTileRows + (uint64_t)tid * 4);
+    }
+    for (; t < end; t += kTileRows) {  // the chunk's tail
+        const uint64_t row = t + (uint64_t)tid * 4;
+        if (t + kTileRows <= end) {    // block-uniform
+            int4 k[NK];
+#pragma unroll
+            for (int j = 0; j < NK; j++) k[j] = load4_nt<VEC>(a.keys[j] + row);
+            pack(k, row);
+        } else {                       // the last ragged tile: row by row, none past the end
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (row + e < end) {
+                    int r[NK];
+#pragma unroll
+                    for (int j = 0; j < NK; j++) r[j] = a.keys[j][row + e];
+                    bool ok;
+                    const uint32_t c = row_code<NK>(a, r, &ok);
+                    nbad += ok ? 0u : 1u;
+                    out[row + e] = (int)(c ^ 0x80000000u);
+                }
+        }
+    }
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+}
+
+// One block: *total = the sum of k_group_by_pack's counts.
+__global__ __launch_bounds__(kTPB) void k_group_by_bad(const uint32_t* __restrict__ bad, uint32_t nbad, u64* __restrict__ total) {
+    __shared__ u64 s_b[kWaves];
+    u64 b = 0;
+    for (uint32_t i = threadIdx.x; i < nbad; i += kTPB) b += bad[i];
+    b = wave_sum_u64(b);
+    if ((threadIdx.x & 63) == 0) s_b[threadIdx.x >> 6] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) *total = s_b[0] + s_b[1] + s_b[2] + s_b[3];
+}
+
+// codes[i] ^ flip is group i's code (flip: 0 for the dense path's slots, 0x80000000 for the
+// sorted column); component j goes to o.keys[j][i] where that is wanted. A range of one needs
+// no division (and its stride may be the 2^32 that a.stride holds as 0); every other
+// component's stride is at most 2^31.
+__global__ __launch_bounds__(kTPB) void k_group_by_unpack(const int32_t* __restrict__ codes, u64 groups, ByArgs a, int nkeys,
+                                                          uint32_t flip, ByKeysOut o) {
+    for (u64 i = (u64)blockIdx.x * kTPB + threadIdx.x; i < groups; i += (u64)gridDim.x * kTPB) {
+        const uint32_t c = (uint32_t)codes[i] ^ flip;
+#pragma unroll
+        for (int j = 0; j < kMaxKeys; j++) {
+            if (j >= nkeys || !o.keys[j]) continue;
+            uint32_t d = 0;
+            if (a.rm1[j] != 0u) {
+                d = c / a.stride[j];
+                if (a.rm1[j] != ~0u) d %= a.rm1[j] + 1u;
+            }
+            o.keys[j][i] = (int32_t)(a.lo[j] + d);
+        }
+    }
+}
+
 // ---- the sort path ----
 
 // ccnt[b] = run heads in block b's chunk of the sorted keys; *groups = their total.
@@ -688,12 +977,30 @@ int launch_where_dense(const DevState* s, const WhereArgs& a, const int32_t* key
     return MQ_OK;
 }
 
-// The dense path of both plans; w: the folded predicates of mq_group_where_plan (wvec:
+template <int NK, bool VEC>
+int launch_by_dense(const DevState* s, const ByArgs& a, const int32_t* vals, uint64_t n, uint32_t range, void** scratch_out,
+                    DenseTabs* tabs, uint32_t* blocks_out, hipStream_t st) {
+    uint32_t g;
+    uint64_t rpb;
+    geometry(s, n, reinterpret_cast<const void*>(&k_group_by_dense<NK, VEC>), &g, &rpb);
+    void* scratch = pool_alloc(dense_scratch_bytes(g, range));
+    if (!scratch) return set_err(MQ_ENOMEM, "mq_group_by_plan: scratch allocation failed");
+    *tabs = dense_tabs(scratch, g, range);
+    *scratch_out = scratch;
+    *blocks_out = g;
+    hipLaunchKernelGGL((k_group_by_dense<NK, VEC>), dim3(g), dim3(kTPB), 0, st, a, vals, n, rpb, range, *tabs);
+    LAUNCHCHK("k_group_by_dense");
+    return MQ_OK;
+}
+
+// The dense path of the three plans; w: the folded predicates of mq_group_where_plan (wvec:
 // whether their columns are all 16-byte aligned), or NULL; rows: NULL, or where the sum of
-// the groups' counts goes.
+// the groups' counts goes; by: the nkeys key columns of mq_group_by_plan (keys is not used
+// then), or NULL.
 int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_t* vals, uint64_t n, hipStream_t st,
-               const WhereArgs* w = nullptr, bool wvec = false, uint64_t* rows = nullptr) {
-    const char* who = w ? "mq_group_where_plan" : "mq_group_plan";
+               const WhereArgs* w = nullptr, bool wvec = false, uint64_t* rows = nullptr, const ByArgs* by = nullptr,
+               int nkeys = 0) {
+    const char* who = by ? "mq_group_by_plan" : w ? "mq_group_where_plan" : "mq_group_plan";
     g->tab = static_cast<char*>(pool_alloc(final_bytes(g->range)));
     if (!g->tab) return set_err(MQ_ENOMEM, "%s: table allocation failed", who);
     const FinalTab f = final_tab(g->tab, g->range);
@@ -702,7 +1009,18 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
     uint32_t blocks = 0;
     const bool vk = aligned16(keys), vv = aligned16(vals);
     int rc;
-    if (w)
+    if (by) {
+        bool vec = vv;
+        for (int j = 0; j < nkeys; j++) vec = vec && aligned16(by->keys[j]);
+        auto launch = [&](auto nk) {
+            constexpr int NK = decltype(nk)::value;
+            return vec ? launch_by_dense<NK, true>(s, *by, vals, n, g->range, &scratch, &tabs, &blocks, st)
+                       : launch_by_dense<NK, false>(s, *by, vals, n, g->range, &scratch, &tabs, &blocks, st);
+        };
+        rc = nkeys == 2   ? launch(std::integral_constant<int, 2>{})
+             : nkeys == 3 ? launch(std::integral_constant<int, 3>{})
+                          : launch(std::integral_constant<int, 4>{});
+    } else if (w)
         rc = wvec && vk && vv ? launch_where_dense<true>(s, *w, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
                               : launch_where_dense<false>(s, *w, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st);
     else
@@ -731,6 +1049,7 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
     pool_free(d_rows);
     if (rc) return rc;
+    if (h[1] && by) return set_err(MQ_EINVAL, "%s: %llu rows with a key outside its column's bounds", who, h[1]);
     if (h[1]) return set_err(MQ_EINVAL, "%s: %llu keys outside the bounds [%d, %lld]", who, h[1], g->lo,
                              (long long)g->lo + g->range - 1);
     g->groups = h[0];
@@ -763,6 +1082,93 @@ int plan_sort(mq_group* g, const int32_t* keys, uint64_t n, const int32_t* bound
     HIPCHK(hipMemcpyAsync(&groups, hdr, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     g->groups = groups;
+    return MQ_OK;
+}
+
+template <int NK, bool VEC>
+int launch_by_pack(const DevState* s, const ByArgs& a, uint64_t n, int32_t* packed, uint32_t** bad_out, uint32_t* nbad_out,
+                   hipStream_t st) {
+    uint32_t g;
+    uint64_t rpb;
+    geometry(s, n, reinterpret_cast<const void*>(&k_group_by_pack<NK, VEC>), &g, &rpb);
+    uint32_t* bad = static_cast<uint32_t*>(pool_alloc((size_t)g * kWaves * 4));
+    if (!bad) return set_err(MQ_ENOMEM, "mq_group_by_plan: allocation failed");
+    *bad_out = bad;
+    *nbad_out = g * kWaves;
+    hipLaunchKernelGGL((k_group_by_pack<NK, VEC>), dim3(g), dim3(kTPB), 0, st, a, n, rpb, packed, bad);
+    LAUNCHCHK("k_group_by_pack");
+    return MQ_OK;
+}
+
+// The packed sort path: the tuples' codes as one int32 column (freed once it is sorted),
+// the rows out of bounds counted on the way, then plan_sort on it.
+int plan_by_sort(const DevState* s, mq_group* g, const ByArgs& a, int nkeys, uint64_t n, hipStream_t st) {
+    const char* who = "mq_group_by_plan";
+    int32_t* packed = static_cast<int32_t*>(pool_alloc(n * 4));
+    u64* d_total = static_cast<u64*>(pool_alloc(sizeof(u64)));
+    uint32_t* bad = nullptr;
+    uint32_t nbad = 0;
+    int rc = packed && d_total ? MQ_OK : set_err(MQ_ENOMEM, "%s: allocation failed", who);
+    if (!rc) {
+        bool vec = true;
+        for (int j = 0; j < nkeys; j++) vec = vec && aligned16(a.keys[j]);
+        auto launch = [&](auto nk) {
+            constexpr int NK = decltype(nk)::value;
+            return vec ? launch_by_pack<NK, true>(s, a, n, packed, &bad, &nbad, st)
+                       : launch_by_pack<NK, false>(s, a, n, packed, &bad, &nbad, st);
+        };
+        rc = nkeys == 2   ? launch(std::integral_constant<int, 2>{})
+             : nkeys == 3 ? launch(std::integral_constant<int, 3>{})
+                          : launch(std::integral_constant<int, 4>{});
+    }
+    u64 total = 0;
+    if (!rc) {
+        hipLaunchKernelGGL(k_group_by_bad, dim3(1), dim3(kTPB), 0, st, bad, nbad, d_total);
+        if (hipGetLastError() != hipSuccess) rc = set_err(MQ_EHIP, "launch of k_group_by_bad failed");
+    }
+    if (!rc && hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = set_err(MQ_EHIP, "%s: count download failed", who);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+    pool_free(bad);
+    pool_free(d_total);
+    if (!rc && total) rc = set_err(MQ_EINVAL, "%s: %llu rows with a key outside its column's bounds", who, total);
+    if (!rc) rc = plan_sort(g, packed, n, nullptr, st);  // synchronises
+    pool_free_on(packed, st);
+    return rc;
+}
+
+// *space = prod(hi_j - lo_j + 1) over the nkeys {lo, hi} pairs of b, saturated at 2^63;
+// false: a lo > hi.
+bool by_space(const int32_t* b, int nkeys, uint64_t* space) {
+    uint64_t p = 1;
+    for (int j = 0; j < nkeys; j++) {
+        if (b[2 * j] > b[2 * j + 1]) return false;
+        const uint64_t r = (uint64_t)((int64_t)b[2 * j + 1] - (int64_t)b[2 * j] + 1);  // up to 2^32
+        p = p > (1ull << 63) / r ? 1ull << 63 : p * r;
+    }
+    *space = p;
+    return true;
+}
+
+// The write of mq_group_write and mq_group_by_write: keys_out receives the key (one key
+// column), the slot (dense, nkeys > 1) or the sorted code (sort, nkeys > 1) of every group.
+int write_groups(mq_group* g, int32_t* keys_out, uint64_t* d_count_out, int64_t* d_sum_out, int32_t* d_min_out,
+                 int32_t* d_max_out, hipStream_t st) {
+    u64* cnt = reinterpret_cast<u64*>(d_count_out);
+    long long* sum = reinterpret_cast<long long*>(d_sum_out);
+    if (g->path == MQ_GROUP_DENSE) {
+        hipLaunchKernelGGL(k_group_dense_write, dim3((g->range + kTPB - 1) / kTPB), dim3(kTPB), 0, st,
+                           final_tab(g->tab, g->range), g->range, g->lo, keys_out, cnt, sum, d_min_out, d_max_out);
+        LAUNCHCHK("k_group_dense_write");
+        return MQ_OK;
+    }
+    const GroupOut o = {keys_out, cnt, sum, d_min_out, d_max_out, g->groups};
+    const int need_vals = d_sum_out || d_min_out || d_max_out;
+    hipLaunchKernelGGL(k_group_seg_init, dim3(1), dim3(kTPB), 0, st, g->ccnt + 4, g->blocks, o);
+    LAUNCHCHK("k_group_seg_init");
+    hipLaunchKernelGGL(k_group_seg_write, dim3(g->blocks), dim3(kTPB), 0, st, g->sorted, g->pos, g->vals, (uint32_t)g->n,
+                       g->chunk, g->ccnt + 4, need_vals, o);
+    LAUNCHCHK("k_group_seg_write");
     return MQ_OK;
 }
 
@@ -1010,25 +1416,153 @@ int mq_group_write(mq_group* g, int32_t* d_keys_out, uint64_t* d_count_out, int6
     int dev = -1;
     if ((rc = current_device(&dev))) return rc;
     if (dev != g->dev) return set_err(MQ_EINVAL, "mq_group_write: the plan was made on device %d", g->dev);
+    if (g->nkeys > 1 && d_keys_out)
+        return set_err(MQ_EINVAL, "mq_group_write: one column cannot hold a %d-key tuple (mq_group_by_write)", g->nkeys);
     if (g->groups == 0) return MQ_OK;
     hipStream_t st = (hipStream_t)stream;
     g->stream = st;
-    u64* cnt = reinterpret_cast<u64*>(d_count_out);
-    long long* sum = reinterpret_cast<long long*>(d_sum_out);
-    if (g->path == MQ_GROUP_DENSE) {
-        hipLaunchKernelGGL(k_group_dense_write, dim3((g->range + kTPB - 1) / kTPB), dim3(kTPB), 0, st,
-                           final_tab(g->tab, g->range), g->range, g->lo, d_keys_out, cnt, sum, d_min_out, d_max_out);
-        LAUNCHCHK("k_group_dense_write");
+    return write_groups(g, d_keys_out, d_count_out, d_sum_out, d_min_out, d_max_out, st);
+}
+
+int mq_group_by_auto_path(const int32_t* h_key_bounds, int nkeys, uint64_t* h_space) {
+    if (h_space) *h_space = 0;
+    if (nkeys < 1 || nkeys > kMaxKeys) return set_err(MQ_EINVAL, "mq_group_by_auto_path: nkeys %d outside 1..%d", nkeys, kMaxKeys);
+    if (!h_key_bounds) return set_err(MQ_EINVAL, "mq_group_by_auto_path: NULL pointer");
+    uint64_t space;
+    if (!by_space(h_key_bounds, nkeys, &space)) return set_err(MQ_EINVAL, "mq_group_by_auto_path: a column's bounds are empty");
+    if (h_space) *h_space = space;
+    if (space > (1ull << 32))
+        return set_err(MQ_EINVAL, "mq_group_by_auto_path: the key space %llu is wider than 2^32", (u64)space);
+    return space <= kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
+}
+
+int mq_group_by_plan(const int32_t* const* d_keys, int nkeys, const int32_t* d_vals, uint64_t n, const int32_t* h_key_bounds,
+                     int path, mq_group** out, uint64_t* h_groups, int* h_path, void* stream) {
+    const char* who = "mq_group_by_plan";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (out) *out = nullptr;
+    if (h_groups) *h_groups = 0;
+    if (nkeys < 1 || nkeys > kMaxKeys) return set_err(MQ_EINVAL, "%s: nkeys %d outside 1..%d", who, nkeys, kMaxKeys);
+    if (!out || !h_groups || (n && (!d_keys || !d_vals))) return set_err(MQ_EINVAL, "%s: NULL pointer", who);
+    if (nkeys == 1) return mq_group_plan(d_keys ? d_keys[0] : nullptr, d_vals, n, h_key_bounds, path, out, h_groups, h_path, stream);
+    if (path != MQ_GROUP_AUTO && path != MQ_GROUP_DENSE && path != MQ_GROUP_SORT)
+        return set_err(MQ_EINVAL, "%s: path %d", who, path);
+    if (n >= (1ull << 31)) return set_err(MQ_EINVAL, "%s: n >= 2^31", who);
+    if (n) {
+        for (int j = 0; j < nkeys; j++)
+            if (!d_keys[j] || (reinterpret_cast<uintptr_t>(d_keys[j]) & 3u))
+                return set_err(MQ_EINVAL, "%s: key column %d NULL or not 4-byte aligned", who, j);
+        if (reinterpret_cast<uintptr_t>(d_vals) & 3u) return set_err(MQ_EINVAL, "%s: value column not 4-byte aligned", who);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    int32_t b[2 * kMaxKeys];
+    uint64_t space = 0;
+    if (n && h_key_bounds) {
+        for (int j = 0; j < 2 * nkeys; j++) b[j] = h_key_bounds[j];
+    } else if (n) {  // one more read of every key column
+        char* ws = static_cast<char*>(pool_alloc(partial_bytes() + kMaxKeys * sizeof(mq_agg)));
+        if (!ws) return set_err(MQ_ENOMEM, "%s: workspace allocation failed", who);
+        mq_agg a[kMaxKeys] = {};
+        mq_agg* d_agg = reinterpret_cast<mq_agg*>(ws + partial_bytes());
+        for (int j = 0; j < nkeys && !rc; j++) rc = mq_reduce(d_keys[j], n, d_agg + j, ws, partial_bytes(), stream);
+        if (!rc && hipMemcpyAsync(a, d_agg, nkeys * sizeof(mq_agg), hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "%s: bounds download failed", who);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+        pool_free(ws);
+        if (rc) return rc;
+        for (int j = 0; j < nkeys; j++) {
+            b[2 * j] = a[j].min;
+            b[2 * j + 1] = a[j].max;
+        }
+    }
+    if (n) {
+        if (!by_space(b, nkeys, &space)) return set_err(MQ_EINVAL, "%s: a column's bounds are empty", who);
+        if (space > (1ull << 32))
+            return set_err(MQ_EINVAL, "%s: the key space %llu (saturated at 2^63) is wider than 2^32", who, (u64)space);
+        if (path == MQ_GROUP_DENSE && space > kDenseSlots)
+            return set_err(MQ_EINVAL, "%s: the key space %llu exceeds the dense path's %u slots", who, (u64)space, kDenseSlots);
+    }
+    mq_group* g = new (std::nothrow) mq_group();
+    if (!g) return set_err(MQ_ENOMEM, "%s: out of host memory", who);
+    g->dev = dev;
+    g->n = n;
+    g->vals = d_vals;
+    g->stream = st;
+    g->nkeys = nkeys;
+    if (n == 0) {
+        g->path = path == MQ_GROUP_SORT ? MQ_GROUP_SORT : MQ_GROUP_DENSE;
+        if (h_path) *h_path = g->path;
+        *out = g;
         return MQ_OK;
     }
-    const GroupOut o = {d_keys_out, cnt, sum, d_min_out, d_max_out, g->groups};
-    const int need_vals = d_sum_out || d_min_out || d_max_out;
-    hipLaunchKernelGGL(k_group_seg_init, dim3(1), dim3(kTPB), 0, st, g->ccnt + 4, g->blocks, o);
-    LAUNCHCHK("k_group_seg_init");
-    hipLaunchKernelGGL(k_group_seg_write, dim3(g->blocks), dim3(kTPB), 0, st, g->sorted, g->pos, g->vals, (uint32_t)g->n,
-                       g->chunk, g->ccnt + 4, need_vals, o);
-    LAUNCHCHK("k_group_seg_write");
+    g->path = path != MQ_GROUP_AUTO ? path : space <= kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
+    ByArgs a = {};
+    uint64_t stride = 1;  // up to the key space
+    for (int j = nkeys - 1; j >= 0; j--) {
+        a.keys[j] = d_keys[j];
+        a.lo[j] = (uint32_t)b[2 * j];
+        a.rm1[j] = (uint32_t)((int64_t)b[2 * j + 1] - (int64_t)b[2 * j]);
+        a.stride[j] = (uint32_t)stride;
+        g->klo[j] = b[2 * j];
+        g->krm1[j] = a.rm1[j];
+        g->kstride[j] = a.stride[j];
+        stride *= (uint64_t)a.rm1[j] + 1;
+    }
+    if (g->path == MQ_GROUP_DENSE) {
+        g->lo = 0;  // the table is addressed by the code
+        g->range = (uint32_t)space;
+        rc = plan_dense(s, g, nullptr, d_vals, n, st, nullptr, false, nullptr, &a, nkeys);
+    } else {
+        rc = plan_by_sort(s, g, a, nkeys, n, st);
+    }
+    if (rc) {
+        release(g, st);
+        return rc;
+    }
+    if (h_path) *h_path = g->path;
+    *h_groups = g->groups;
+    *out = g;
     return MQ_OK;
+}
+
+int mq_group_by_write(mq_group* g, int32_t* const* d_keys_out, uint64_t* d_count_out, int64_t* d_sum_out, int32_t* d_min_out,
+                      int32_t* d_max_out, void* stream) {
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (!g) return set_err(MQ_EINVAL, "mq_group_by_write: NULL handle");
+    if (g->nkeys <= 1) return mq_group_write(g, d_keys_out ? d_keys_out[0] : nullptr, d_count_out, d_sum_out, d_min_out, d_max_out, stream);
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    if (dev != g->dev) return set_err(MQ_EINVAL, "mq_group_by_write: the plan was made on device %d", g->dev);
+    if (g->groups == 0) return MQ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    g->stream = st;
+    ByArgs a = {};
+    ByKeysOut o = {};
+    bool want = false;
+    for (int j = 0; j < g->nkeys; j++) {
+        a.lo[j] = (uint32_t)g->klo[j];
+        a.rm1[j] = g->krm1[j];
+        a.stride[j] = g->kstride[j];
+        o.keys[j] = d_keys_out ? d_keys_out[j] : nullptr;
+        want = want || o.keys[j];
+    }
+    int32_t* codes = nullptr;  // the groups' slots or sorted codes
+    if (want && !(codes = static_cast<int32_t*>(pool_alloc(g->groups * 4))))
+        return set_err(MQ_ENOMEM, "mq_group_by_write: allocation failed");
+    rc = write_groups(g, codes, d_count_out, d_sum_out, d_min_out, d_max_out, st);
+    if (!rc && codes) {
+        hipLaunchKernelGGL(k_group_by_unpack, dim3(stream_grid(s, g->groups)), dim3(kTPB), 0, st, codes, (u64)g->groups, a,
+                           g->nkeys, g->path == MQ_GROUP_DENSE ? 0u : 0x80000000u, o);
+        if (hipGetLastError() != hipSuccess) rc = set_err(MQ_EHIP, "launch of k_group_by_unpack failed");
+    }
+    pool_free_on(codes, st);  // k_group_by_unpack is its last reader
+    return rc;
 }
 
 int mq_group_free(mq_group* g) {

@@ -1089,17 +1089,20 @@ static Result* long_result_from_device(const void* d_src, size_t n, Status* st) 
     return new_result(LONG, n, host);
 }
 
-/* The five Results of a planned group handle, which is freed here: keys (INT), count (LONG),
- * sum (LONG), min (INT), max (INT), one entry per group. rc: the plan's return code. */
-static Result** group_results(const char* who, mq_group* g, uint64_t groups, int rc, Status* ret_status) {
+/* The nkeys + 4 Results of a planned group handle, which is freed here: the nkeys key columns
+ * (INT), then count (LONG), sum (LONG), min (INT), max (INT), one entry per group. rc: the
+ * plan's return code. */
+static Result** group_results(const char* who, mq_group* g, uint64_t groups, int nkeys, int rc, Status* ret_status) {
     void* buf = NULL;
-    /* one block: count and sum (8 bytes an entry) first, then keys, min and max */
-    if (!rc) rc = dev_alloc(&buf, groups ? (size_t)groups * 28 : 16);
+    const int nres = nkeys + 4;
+    /* one block: count and sum (8 bytes an entry) first, then the keys, min and max */
+    if (!rc) rc = dev_alloc(&buf, groups ? (size_t)groups * (16 + 4 * (size_t)(nkeys + 2)) : 16);
     uint64_t* d_count = (uint64_t*)buf;
     int64_t* d_sum = (int64_t*)(d_count + groups);
-    int32_t* d_keys = (int32_t*)(d_sum + groups);
-    int32_t *d_min = d_keys + groups, *d_max = d_min + groups;
-    if (!rc) rc = mq_group_write(g, d_keys, d_count, d_sum, d_min, d_max, g_stream);
+    int32_t* d_keys[MQ_GROUP_MAX_KEYS];
+    for (int j = 0; j < nkeys; j++) d_keys[j] = (int32_t*)(d_sum + groups) + (size_t)j * groups;
+    int32_t *d_min = d_keys[nkeys - 1] + groups, *d_max = d_min + groups;
+    if (!rc) rc = mq_group_by_write(g, d_keys, d_count, d_sum, d_min, d_max, g_stream);
     mq_group_free(g); /* in g_stream's order, behind the write */
     if (rc) {
         mq_stream_sync(g_stream);
@@ -1107,17 +1110,17 @@ static Result** group_results(const char* who, mq_group* g, uint64_t groups, int
         fail(ret_status, who, rc);
         return NULL;
     }
-    Result** out = (Result**)calloc(5, sizeof(Result*));
-    out[0] = int_result_from_device(d_keys, (size_t)groups, ret_status);
-    out[1] = long_result_from_device(d_count, (size_t)groups, ret_status);
-    out[2] = long_result_from_device(d_sum, (size_t)groups, ret_status);
-    out[3] = int_result_from_device(d_min, (size_t)groups, ret_status);
-    out[4] = int_result_from_device(d_max, (size_t)groups, ret_status);
+    Result** out = (Result**)calloc((size_t)nres, sizeof(Result*));
+    for (int j = 0; j < nkeys; j++) out[j] = int_result_from_device(d_keys[j], (size_t)groups, ret_status);
+    out[nkeys] = long_result_from_device(d_count, (size_t)groups, ret_status);
+    out[nkeys + 1] = long_result_from_device(d_sum, (size_t)groups, ret_status);
+    out[nkeys + 2] = int_result_from_device(d_min, (size_t)groups, ret_status);
+    out[nkeys + 3] = int_result_from_device(d_max, (size_t)groups, ret_status);
     mq_stream_sync(g_stream);
     mq_pool_free(buf);
-    for (int i = 0; i < 5; i++)
+    for (int i = 0; i < nres; i++)
         if (!out[i]) {
-            for (int j = 0; j < 5; j++)
+            for (int j = 0; j < nres; j++)
                 if (out[j]) {
                     free(out[j]->payload);
                     free(out[j]);
@@ -1153,7 +1156,7 @@ Result** group_aggregate(GeneralizedColumn* keys, GeneralizedColumn* values, Sta
     mq_group* g = NULL;
     uint64_t groups = 0;
     const int rc = mq_group_plan(dk, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, g_stream);
-    return group_results("group_aggregate", g, groups, rc, ret_status);
+    return group_results("group_aggregate", g, groups, 1, rc, ret_status);
 }
 
 /* The first min(k, rows) entries of `values` in ascending or descending order, equal values
@@ -1333,7 +1336,40 @@ Result** group_aggregate_where(GeneralizedColumn** columns, int** lows, int** hi
     uint64_t groups = 0;
     const int rc = mq_group_where_plan(d_cols, ranges, ncols, dk, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, NULL,
                                        g_stream);
-    return group_results(who, g, groups, rc, ret_status);
+    return group_results(who, g, groups, 1, rc, ret_status);
+}
+
+/* group_aggregate by the tuple of `nkeys` key columns, in lexicographic order (no reference
+ * counterpart): nkeys + 4 Results, the key columns (INT) first. No key bounds
+ * are passed (group_aggregate's reason): the plan reads every key column once more for them. */
+Result** group_aggregate_by(GeneralizedColumn** keys, int nkeys, GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "group_aggregate_by";
+    if (nkeys < 1 || nkeys > MQ_GROUP_MAX_KEYS) {
+        dml_fail(ret_status, who, "nkeys outside 1..4");
+        return NULL;
+    }
+    const int32_t* dk[MQ_GROUP_MAX_KEYS];
+    const int32_t* dv = NULL;
+    size_t n = 0, m = 0;
+    int bad = !keys || !values, differ = 0;
+    for (int j = 0; j <= nkeys && !bad; j++) { /* the key columns, then the values */
+        GeneralizedColumn* gc = j < nkeys ? keys[j] : values;
+        const int a = gc ? gcol_device(gc, j < nkeys ? &dk[j] : &dv, &m, ret_status) : -1;
+        if (a > 0) return NULL;
+        bad = a < 0;
+        if (j == 0) n = m;
+        differ = differ || m != n;
+    }
+    if (bad || differ) {
+        dml_fail(ret_status, who,
+                 bad ? "keys and values must each be a Column or an INT Result" : "the keys and values differ in length");
+        return NULL;
+    }
+    mq_group* g = NULL;
+    uint64_t groups = 0;
+    const int rc = mq_group_by_plan(dk, nkeys, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, g_stream);
+    return group_results(who, g, groups, nkeys, rc, ret_status);
 }
 
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner

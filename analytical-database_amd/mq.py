@@ -24,6 +24,7 @@ INT, LONG, FLOAT, DOUBLE = 0, 1, 2, 3
 OK, ERROR = 0, 1
 RESULT, COLUMN = 0, 1
 MQ_GROUP_AUTO, MQ_GROUP_DENSE, MQ_GROUP_SORT = 0, 1, 2
+MQ_GROUP_MAX_KEYS = 4
 MQ_TOPK_AUTO, MQ_TOPK_SELECT, MQ_TOPK_SORT = 0, 1, 2
 MQ_TOPK_SORT_DIV = 4
 MQ_WHERE_MAX_COLS = 8
@@ -196,6 +197,10 @@ _SIGS = {
     "mq_group_free": (_int, [_vp]),
     "mq_group_where_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _vp, _u64, _vp, _int, C.POINTER(_vp),
                                    C.POINTER(_u64), C.POINTER(_int), C.POINTER(_u64), _vp]),
+    "mq_group_by_auto_path": (_int, [C.POINTER(_i32), _int, C.POINTER(_u64)]),
+    "mq_group_by_plan": (_int, [C.POINTER(_vp), _int, _vp, _u64, C.POINTER(_i32), _int, C.POINTER(_vp), C.POINTER(_u64),
+                                C.POINTER(_int), _vp]),
+    "mq_group_by_write": (_int, [_vp, C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
     "mq_topk_default_cap": (_u64, []),
     "mq_topk_auto_path": (_int, [_u64, _u64, _u64]),
     "mq_topk": (_int, [_vp, _vp, _u64, _u64, _int, _int, _u64, _vp, _vp, C.POINTER(MqTopkInfo), _vp]),
@@ -253,6 +258,8 @@ _SIGS = {
     "group_aggregate_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
                                                C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn),
                                                C.POINTER(GeneralizedColumn), _PS]),
+    "group_aggregate_by": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), _int, C.POINTER(GeneralizedColumn),
+                                            _PS]),
     "log_result": (None, [_PR]),
     "should_use_index": (C.c_bool, [C.POINTER(Column), _int, _int]),
     # load path (db_manager.h:254)

@@ -348,6 +348,23 @@ Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, i
 Result** group_aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
                                GeneralizedColumn* keys, GeneralizedColumn* values, Status* ret_status);
 
+/* ---- GROUP BY over several key columns (not in the reference) ----
+ * group_aggregate_by: SELECT k0, .., count(*), sum(v), min(v), max(v) FROM t GROUP BY k0, ..
+ * over nkeys = 1..MQ_GROUP_MAX_KEYS (4) key columns (mq_group_by_plan /
+ * mq_group_by_write in mq_device.h). Each of keys[0..nkeys) and `values` is a COLUMN or an
+ * INT RESULT, as group_aggregate takes them, all equally long; any of them may be the same
+ * object. Returns a malloc'd array of nkeys + 4 Result* under group_aggregate's ownership
+ * and shadow rules, one tuple per distinct (k0, .., k_{nkeys-1}), in ascending lexicographic
+ * order with k0 the most significant: [0 .. nkeys) the key columns (INT), then counts (LONG),
+ * sums (LONG), minima (INT) and maxima (INT). No rows give nkeys + 4 empty Results and OK.
+ * No key bounds are passed, for group_aggregate's reason: every key column is read once more
+ * for its range, and the product of the ranges picks the path (up to mq_group_dense_slots()
+ * the one-pass table in LDS, up to 2^32 one packed column and the sort path). Runs on the
+ * calling device; a column held as row shards drops them and is split again on next use.
+ * ERROR and NULL (a "libmq:" line on stderr): group_aggregate's cases, nkeys outside 1..4, a
+ * key space (the product of the columns' ranges) wider than 2^32. */
+Result** group_aggregate_by(GeneralizedColumn** keys, int nkeys, GeneralizedColumn* values, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
