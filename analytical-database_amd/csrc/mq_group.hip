@@ -68,6 +68,18 @@
 //   k_group_by_unpack  : the write kernels put each group's slot or code into a temporary;
 //                        this decodes it into the key outputs, K_j = lo_j + (code / stride_j)
 //                        % range_j.
+//
+// mq_group_by_where_plan is mq_group_by_plan over the rows for which a
+// conjunction of range predicates holds, on the same handle:
+//   k_group_by_where_dense : (P <= kDenseSlots) k_group_where_dense's stream over the
+//                        predicate columns and the surviving lines of the nkeys + 1 columns,
+//                        k_group_by_dense's code as the slot, live rows only.
+//   k_group_by_where_bounds: (no bounds given) every key column's min and max over the
+//                        matching rows and their number in one pass, one ByBounds a block;
+//                        k_group_by_where_bounds_fold combines them.
+//   k_group_by_pack_pos: (P <= 2^32) code ^ 0x80000000 of the K matching rows, read from the
+//                        key columns through mq_where_positions' positions; the values are
+//                        gathered with mq_fetch and the sort path runs on the K codes.
 
 #include <hip/hip_runtime.h>
 
@@ -777,6 +789,347 @@ __global__ __launch_bounds__(kTPB) void k_group_by_unpack(const int32_t* __restr
     }
 }
 
+// ---- a tuple of key columns under predicates (mq_group_by_where_plan) ----
+
+// Tiles in flight per thread under predicates: by_tiles' (nkeys + 1) * U dwordx4 of loaded
+// data a lane, with the live nibbles beside them (the ballots are scalar).
+constexpr int bw_tiles(int nkeys) { return by_tiles(nkeys); }
+
+// k_group_by_dense over the rows that survive the predicates of `w`, k_group_where_dense's
+// stream: of the NK key columns and the value column only the 128-byte lines that hold a
+// survivor are requested. A row whose bit is clear has nothing loaded behind it in a dead line
+// and anything at all in a live one: its code and its bounds bit are never used.
+template <int NK, bool VEC>
+__global__ __launch_bounds__(kTPB, 4) void k_group_by_where_dense(WhereArgs w, ByArgs a, const int* vals, uint64_t n,
+                                                                  uint64_t rows_per_block, uint32_t range, DenseTabs out) {
+    constexpr int U = bw_tiles(NK);
+    __shared__ uint32_t s_cnt[kDenseSlots];
+    __shared__ u64 s_sum[kDenseSlots];
+    __shared__ int s_mn[kDenseSlots];
+    __shared__ int s_mx[kDenseSlots];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        s_cnt[s] = 0u;
+        s_sum[s] = 0ull;
+        s_mn[s] = INT_MAX;
+        s_mx[s] = INT_MIN;
+    }
+    __syncthreads();
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    uint32_t nbad = 0;  // live rows only
+    // the wave's run of tiles whose surviving rows all share run_slot, folded per lane
+    uint32_t run_slot = 0;
+    bool run_open = false;  // wave-uniform
+    uint32_t r_cnt = 0;
+    long long r_sum = 0;
+    int r_mn = INT_MAX, r_mx = INT_MIN;
+
+    auto update = [&](uint32_t s, int v) {
+        if (s < range) {  // kNoSlot never is
+            atomicAdd(&s_cnt[s], 1u);
+            atomicAdd(&s_sum[s], (u64)(long long)v);
+            atomicMin(&s_mn[s], v);
+            atomicMax(&s_mx[s], v);
+        } else {
+            nbad++;
+        }
+    };
+    auto flush = [&]() {  // wave-uniform
+        const uint32_t c = (uint32_t)wave_sum_u64(r_cnt);  // <= the rows of the block's chunk < 2^31
+        const long long sm = wave_sum_i64(r_sum);
+        const int mn = wave_min(r_mn), mx = wave_max(r_mx);
+        if (lane == 0) {
+            if (run_slot < range) {
+                atomicAdd(&s_cnt[run_slot], c);
+                atomicAdd(&s_sum[run_slot], (u64)sm);
+                atomicMin(&s_mn[run_slot], mn);
+                atomicMax(&s_mx[run_slot], mx);
+            } else {
+                nbad += c;
+            }
+        }
+        run_open = false;
+        r_cnt = 0;
+        r_sum = 0;
+        r_mn = INT_MAX;
+        r_mx = INT_MIN;
+    };
+    // A full tile with a survivor in the wave (b: the lanes that hold one); k and v are loaded
+    // in the lanes whose line is live, so in every lane with a bit set.
+    auto consume = [&](const int4 (&k)[NK], int4 v, uint32_t live, u64 b) {
+        uint32_t in;
+        const uint4 c = tile_codes<NK>(a, k, &in);  // of a dead row: never read below
+        const uint32_t sx = in & 1u ? c.x : kNoSlot, sy = in & 2u ? c.y : kNoSlot, sz = in & 4u ? c.z : kNoSlot,
+                       sw = in & 8u ? c.w : kNoSlot;
+        const uint32_t sf = live & 1u ? sx : live & 2u ? sy : live & 4u ? sz : sw;  // the lane's first surviving slot
+        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane((int)sf, __builtin_ctzll(b));
+        const bool same = live == 0u || ((!(live & 1u) || sx == s0) && (!(live & 2u) || sy == s0) &&
+                                         (!(live & 4u) || sz == s0) && (!(live & 8u) || sw == s0));
+        if (__all(same)) {  // the surviving rows of the wave's 256 share one slot: into the run
+            if (run_open && s0 != run_slot) flush();
+            run_slot = s0;
+            run_open = true;
+            r_cnt += (uint32_t)__popc(live);
+            r_sum += (live & 1u ? (long long)v.x : 0ll) + (live & 2u ? (long long)v.y : 0ll) +
+                     (live & 4u ? (long long)v.z : 0ll) + (live & 8u ? (long long)v.w : 0ll);
+            r_mn = min(r_mn, min(min(live & 1u ? v.x : INT_MAX, live & 2u ? v.y : INT_MAX),
+                                 min(live & 4u ? v.z : INT_MAX, live & 8u ? v.w : INT_MAX)));
+            r_mx = max(r_mx, max(max(live & 1u ? v.x : INT_MIN, live & 2u ? v.y : INT_MIN),
+                                 max(live & 4u ? v.z : INT_MIN, live & 8u ? v.w : INT_MIN)));
+        } else {
+            if (live & 1u) update(sx, v.x);
+            if (live & 2u) update(sy, v.y);
+            if (live & 4u) update(sz, v.z);
+            if (live & 8u) update(sw, v.w);
+        }
+    };
+    // T full tiles: every key and value load of the iteration is issued before the first use
+    auto tiles = [&](auto tc, uint64_t t) {
+        constexpr int T = decltype(tc)::value;
+        const uint64_t row = t + (uint64_t)tid * 4;
+        uint32_t live[T];
+        live_tiles<VEC, T>(w, row, lane, live);
+        u64 b[T];
+        int4 k[T][NK], v[T];
+#pragma unroll
+        for (int u = 0; u < T; u++) b[u] = __ballot(live[u] != 0u);
+#pragma unroll
+        for (int j = 0; j < NK; j++)
+#pragma unroll
+            for (int u = 0; u < T; u++)
+                if (b[u] != 0 && line_live(b[u], lane)) k[u][j] = load4_nt<VEC>(a.keys[j] + row + (uint64_t)u * kTileRows);
+#pragma unroll
+        for (int u = 0; u < T; u++)
+            if (b[u] != 0 && line_live(b[u], lane)) v[u] = load4_nt<VEC>(vals + row + (uint64_t)u * kTileRows);
+#pragma unroll
+        for (int u = 0; u < T; u++)
+            if (b[u] != 0) consume(k[u], v[u], live[u], b[u]);  // wave-uniform
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)U * kTileRows <= end; t += (uint64_t)U * kTileRows) tiles(std::integral_constant<int, U>{}, t);
+    for (; t + kTileRows <= end; t += kTileRows) tiles(std::integral_constant<int, 1>{}, t);
+    if (t < end) {  // the column's ragged tile: row by row, none past the end
+        const uint64_t row = t + (uint64_t)tid * 4;
+        const uint32_t live = live_ragged(w, row, end);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (live & (1u << e)) {
+                int r[NK];
+#pragma unroll
+                for (int j = 0; j < NK; j++) r[j] = a.keys[j][row + e];
+                bool ok;
+                const uint32_t c = row_code<NK>(a, r, &ok);
+                update(ok ? c : kNoSlot, vals[row + e]);
+            }
+    }
+    if (run_open) flush();
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) out.bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * range;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        out.cnt[base + s] = s_cnt[s];
+        out.sum[base + s] = (long long)s_sum[s];
+        out.mn[base + s] = s_mn[s];
+        out.mx[base + s] = s_mx[s];
+    }
+}
+
+// The matching rows' number and every key column's min and max over them (the identity for a
+// column that is not there).
+struct ByBounds {
+    u64 count;
+    int mn[kMaxKeys];
+    int mx[kMaxKeys];
+};
+
+// One pass over the predicates and the surviving lines of all NK key columns: one ByBounds a
+// block, combined by k_group_by_where_bounds_fold.
+template <int NK, bool VEC>
+__global__ __launch_bounds__(kTPB, 8) void k_group_by_where_bounds(WhereArgs w, ByArgs a, uint64_t n, uint64_t rows_per_block,
+                                                                   ByBounds* __restrict__ part) {
+    constexpr int U = bw_tiles(NK);
+    __shared__ ByBounds sp[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    uint32_t cnt = 0;
+    int mn[NK], mx[NK];
+#pragma unroll
+    for (int j = 0; j < NK; j++) {
+        mn[j] = INT_MAX;
+        mx[j] = INT_MIN;
+    }
+    auto fold = [&](int j, int4 k, uint32_t live) {
+        mn[j] = min(mn[j], min(min(live & 1u ? k.x : INT_MAX, live & 2u ? k.y : INT_MAX),
+                               min(live & 4u ? k.z : INT_MAX, live & 8u ? k.w : INT_MAX)));
+        mx[j] = max(mx[j], max(max(live & 1u ? k.x : INT_MIN, live & 2u ? k.y : INT_MIN),
+                               max(live & 4u ? k.z : INT_MIN, live & 8u ? k.w : INT_MIN)));
+    };
+    auto tiles = [&](auto tc, uint64_t t) {
+        constexpr int T = decltype(tc)::value;
+        const uint64_t row = t + (uint64_t)tid * 4;
+        uint32_t live[T];
+        live_tiles<VEC, T>(w, row, lane, live);
+        u64 b[T];
+        int4 k[T][NK];
+#pragma unroll
+        for (int u = 0; u < T; u++) b[u] = __ballot(live[u] != 0u);
+#pragma unroll
+        for (int j = 0; j < NK; j++)
+#pragma unroll
+            for (int u = 0; u < T; u++)
+                if (b[u] != 0 && line_live(b[u], lane)) k[u][j] = load4_nt<VEC>(a.keys[j] + row + (uint64_t)u * kTileRows);
+#pragma unroll
+        for (int u = 0; u < T; u++)
+            if (live[u] != 0u) {
+                cnt += (uint32_t)__popc(live[u]);
+#pragma unroll
+                for (int j = 0; j < NK; j++) fold(j, k[u][j], live[u]);
+            }
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)U * kTileRows <= end; t += (uint64_t)U * kTileRows) tiles(std::integral_constant<int, U>{}, t);
+    for (; t + kTileRows <= end; t += kTileRows) tiles(std::integral_constant<int, 1>{}, t);
+    if (t < end) {  // the column's ragged tile
+        const uint64_t row = t + (uint64_t)tid * 4;
+        const uint32_t live = live_ragged(w, row, end);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (live & (1u << e)) {
+                cnt++;
+#pragma unroll
+                for (int j = 0; j < NK; j++) {
+                    const int k = a.keys[j][row + e];
+                    mn[j] = min(mn[j], k);
+                    mx[j] = max(mx[j], k);
+                }
+            }
+    }
+
+    const u64 wc = wave_sum_u64((u64)cnt);
+#pragma unroll
+    for (int j = 0; j < NK; j++) {
+        mn[j] = wave_min(mn[j]);
+        mx[j] = wave_max(mx[j]);
+    }
+    if (lane == 0) {
+        sp[wave].count = wc;
+#pragma unroll
+        for (int j = 0; j < kMaxKeys; j++) {
+            sp[wave].mn[j] = INT_MAX;
+            sp[wave].mx[j] = INT_MIN;
+        }
+#pragma unroll
+        for (int j = 0; j < NK; j++) {
+            sp[wave].mn[j] = mn[j];
+            sp[wave].mx[j] = mx[j];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        ByBounds r = sp[0];
+#pragma unroll
+        for (int q = 1; q < kWaves; q++) {
+            r.count += sp[q].count;
+#pragma unroll
+            for (int j = 0; j < kMaxKeys; j++) {
+                r.mn[j] = min(r.mn[j], sp[q].mn[j]);
+                r.mx[j] = max(r.mx[j], sp[q].mx[j]);
+            }
+        }
+        part[blockIdx.x] = r;
+    }
+}
+
+// One block: *out = the blocks' ByBounds combined.
+__global__ __launch_bounds__(kTPB) void k_group_by_where_bounds_fold(const ByBounds* __restrict__ part, uint32_t blocks,
+                                                                     ByBounds* __restrict__ out) {
+    __shared__ ByBounds sp[kWaves];
+    ByBounds r;
+    r.count = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxKeys; j++) {
+        r.mn[j] = INT_MAX;
+        r.mx[j] = INT_MIN;
+    }
+    for (uint32_t i = threadIdx.x; i < blocks; i += kTPB) {
+        r.count += part[i].count;
+#pragma unroll
+        for (int j = 0; j < kMaxKeys; j++) {
+            r.mn[j] = min(r.mn[j], part[i].mn[j]);
+            r.mx[j] = max(r.mx[j], part[i].mx[j]);
+        }
+    }
+    r.count = wave_sum_u64(r.count);
+#pragma unroll
+    for (int j = 0; j < kMaxKeys; j++) {
+        r.mn[j] = wave_min(r.mn[j]);
+        r.mx[j] = wave_max(r.mx[j]);
+    }
+    if ((threadIdx.x & 63) == 0) sp[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        r = sp[0];
+#pragma unroll
+        for (int q = 1; q < kWaves; q++) {
+            r.count += sp[q].count;
+#pragma unroll
+            for (int j = 0; j < kMaxKeys; j++) {
+                r.mn[j] = min(r.mn[j], sp[q].mn[j]);
+                r.mx[j] = max(r.mx[j], sp[q].mx[j]);
+            }
+        }
+        *out = r;
+    }
+}
+
+// out[i] = code(row pos[i]) ^ 0x80000000 for the k matching rows, straight from the key
+// columns (grid-stride, four independent rows a lane in flight); bad[block][wave] = the rows
+// with a component out of bounds, as k_group_by_pack keeps them. A position outside [0, n)
+// (mq_where_positions writes none) is counted, never used as an address.
+template <int NK>
+__global__ __launch_bounds__(kTPB) void k_group_by_pack_pos(ByArgs a, const int32_t* __restrict__ pos, uint32_t k, uint32_t n,
+                                                            int32_t* __restrict__ out, uint32_t* __restrict__ bad) {
+    constexpr int kRows = 4;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const u64 stride = (u64)gridDim.x * kTPB;
+    uint32_t nbad = 0;
+    for (u64 i0 = (u64)blockIdx.x * kTPB + tid; i0 < k; i0 += kRows * stride) {
+        uint32_t p[kRows];
+        bool have[kRows];
+        int r[kRows][NK];
+#pragma unroll
+        for (int q = 0; q < kRows; q++) {
+            const u64 i = i0 + q * stride;
+            p[q] = i < k ? (uint32_t)pos[i] : ~0u;
+            have[q] = p[q] < n;
+        }
+#pragma unroll
+        for (int q = 0; q < kRows; q++)
+#pragma unroll
+            for (int j = 0; j < NK; j++) r[q][j] = have[q] ? a.keys[j][p[q]] : 0;
+#pragma unroll
+        for (int q = 0; q < kRows; q++) {
+            const u64 i = i0 + q * stride;
+            if (i >= k) continue;
+            bool ok;
+            const uint32_t c = row_code<NK>(a, r[q], &ok);
+            nbad += ok && have[q] ? 0u : 1u;
+            out[i] = (int)(c ^ 0x80000000u);
+        }
+    }
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+}
+
 // ---- the sort path ----
 
 // ccnt[b] = run heads in block b's chunk of the sorted keys; *groups = their total.
@@ -993,14 +1346,30 @@ int launch_by_dense(const DevState* s, const ByArgs& a, const int32_t* vals, uin
     return MQ_OK;
 }
 
-// The dense path of the three plans; w: the folded predicates of mq_group_where_plan (wvec:
-// whether their columns are all 16-byte aligned), or NULL; rows: NULL, or where the sum of
-// the groups' counts goes; by: the nkeys key columns of mq_group_by_plan (keys is not used
-// then), or NULL.
+template <int NK, bool VEC>
+int launch_by_where_dense(const DevState* s, const WhereArgs& w, const ByArgs& a, const int32_t* vals, uint64_t n, uint32_t range,
+                          void** scratch_out, DenseTabs* tabs, uint32_t* blocks_out, hipStream_t st) {
+    uint32_t g;
+    uint64_t rpb;
+    geometry(s, n, reinterpret_cast<const void*>(&k_group_by_where_dense<NK, VEC>), &g, &rpb, (uint64_t)bw_tiles(NK) * kTileRows);
+    void* scratch = pool_alloc(dense_scratch_bytes(g, range));
+    if (!scratch) return set_err(MQ_ENOMEM, "mq_group_by_where_plan: scratch allocation failed");
+    *tabs = dense_tabs(scratch, g, range);
+    *scratch_out = scratch;
+    *blocks_out = g;
+    hipLaunchKernelGGL((k_group_by_where_dense<NK, VEC>), dim3(g), dim3(kTPB), 0, st, w, a, vals, n, rpb, range, *tabs);
+    LAUNCHCHK("k_group_by_where_dense");
+    return MQ_OK;
+}
+
+// The dense path of the four plans; w: the folded predicates of mq_group_where_plan and
+// mq_group_by_where_plan (wvec: whether their columns are all 16-byte aligned), or NULL; rows:
+// NULL, or where the sum of the groups' counts goes; by: the nkeys key columns of
+// mq_group_by_plan and mq_group_by_where_plan (keys is not used then), or NULL.
 int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_t* vals, uint64_t n, hipStream_t st,
                const WhereArgs* w = nullptr, bool wvec = false, uint64_t* rows = nullptr, const ByArgs* by = nullptr,
                int nkeys = 0) {
-    const char* who = by ? "mq_group_by_plan" : w ? "mq_group_where_plan" : "mq_group_plan";
+    const char* who = by && w ? "mq_group_by_where_plan" : by ? "mq_group_by_plan" : w ? "mq_group_where_plan" : "mq_group_plan";
     g->tab = static_cast<char*>(pool_alloc(final_bytes(g->range)));
     if (!g->tab) return set_err(MQ_ENOMEM, "%s: table allocation failed", who);
     const FinalTab f = final_tab(g->tab, g->range);
@@ -1014,6 +1383,9 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
         for (int j = 0; j < nkeys; j++) vec = vec && aligned16(by->keys[j]);
         auto launch = [&](auto nk) {
             constexpr int NK = decltype(nk)::value;
+            if (w)
+                return vec && wvec ? launch_by_where_dense<NK, true>(s, *w, *by, vals, n, g->range, &scratch, &tabs, &blocks, st)
+                                   : launch_by_where_dense<NK, false>(s, *w, *by, vals, n, g->range, &scratch, &tabs, &blocks, st);
             return vec ? launch_by_dense<NK, true>(s, *by, vals, n, g->range, &scratch, &tabs, &blocks, st)
                        : launch_by_dense<NK, false>(s, *by, vals, n, g->range, &scratch, &tabs, &blocks, st);
         };
@@ -1100,11 +1472,26 @@ int launch_by_pack(const DevState* s, const ByArgs& a, uint64_t n, int32_t* pack
     return MQ_OK;
 }
 
+template <int NK>
+int launch_by_pack_pos(const DevState* s, const ByArgs& a, const int32_t* pos, uint64_t k, uint64_t n, int32_t* packed,
+                       uint32_t** bad_out, uint32_t* nbad_out, hipStream_t st) {
+    const uint32_t g = stream_grid(s, (k + 3) / 4);  // four rows a lane in flight
+    uint32_t* bad = static_cast<uint32_t*>(pool_alloc((size_t)g * kWaves * 4));
+    if (!bad) return set_err(MQ_ENOMEM, "mq_group_by_where_plan: allocation failed");
+    *bad_out = bad;
+    *nbad_out = g * kWaves;
+    hipLaunchKernelGGL((k_group_by_pack_pos<NK>), dim3(g), dim3(kTPB), 0, st, a, pos, (uint32_t)k, (uint32_t)n, packed, bad);
+    LAUNCHCHK("k_group_by_pack_pos");
+    return MQ_OK;
+}
+
 // The packed sort path: the tuples' codes as one int32 column (freed once it is sorted),
-// the rows out of bounds counted on the way, then plan_sort on it.
-int plan_by_sort(const DevState* s, mq_group* g, const ByArgs& a, int nkeys, uint64_t n, hipStream_t st) {
-    const char* who = "mq_group_by_plan";
-    int32_t* packed = static_cast<int32_t*>(pool_alloc(n * 4));
+// the rows out of bounds counted on the way, then plan_sort on it. pos: NULL (all n rows), or
+// the k matching rows' positions of mq_group_by_where_plan (k > 0), whose codes alone are packed.
+int plan_by_sort(const DevState* s, mq_group* g, const ByArgs& a, int nkeys, uint64_t n, hipStream_t st,
+                 const char* who = "mq_group_by_plan", const int32_t* pos = nullptr, uint64_t k = 0) {
+    const uint64_t rows = pos ? k : n;
+    int32_t* packed = static_cast<int32_t*>(pool_alloc(rows * 4));
     u64* d_total = static_cast<u64*>(pool_alloc(sizeof(u64)));
     uint32_t* bad = nullptr;
     uint32_t nbad = 0;
@@ -1114,6 +1501,7 @@ int plan_by_sort(const DevState* s, mq_group* g, const ByArgs& a, int nkeys, uin
         for (int j = 0; j < nkeys; j++) vec = vec && aligned16(a.keys[j]);
         auto launch = [&](auto nk) {
             constexpr int NK = decltype(nk)::value;
+            if (pos) return launch_by_pack_pos<NK>(s, a, pos, k, n, packed, &bad, &nbad, st);
             return vec ? launch_by_pack<NK, true>(s, a, n, packed, &bad, &nbad, st)
                        : launch_by_pack<NK, false>(s, a, n, packed, &bad, &nbad, st);
         };
@@ -1132,9 +1520,27 @@ int plan_by_sort(const DevState* s, mq_group* g, const ByArgs& a, int nkeys, uin
     pool_free(bad);
     pool_free(d_total);
     if (!rc && total) rc = set_err(MQ_EINVAL, "%s: %llu rows with a key outside its column's bounds", who, total);
-    if (!rc) rc = plan_sort(g, packed, n, nullptr, st);  // synchronises
+    if (!rc) rc = plan_sort(g, packed, rows, nullptr, st);  // synchronises
     pool_free_on(packed, st);
     return rc;
+}
+
+// The tuple code of the bounds b (nkeys {lo, hi} pairs whose key space is at most 2^32) over
+// the key columns d_keys, as the kernels take it and as the handle keeps it for the write.
+ByArgs by_args(mq_group* g, const int32_t* const* d_keys, const int32_t* b, int nkeys) {
+    ByArgs a = {};
+    uint64_t stride = 1;  // up to the key space
+    for (int j = nkeys - 1; j >= 0; j--) {
+        a.keys[j] = d_keys[j];
+        a.lo[j] = (uint32_t)b[2 * j];
+        a.rm1[j] = (uint32_t)((int64_t)b[2 * j + 1] - (int64_t)b[2 * j]);
+        a.stride[j] = (uint32_t)stride;
+        g->klo[j] = b[2 * j];
+        g->krm1[j] = a.rm1[j];
+        g->kstride[j] = a.stride[j];
+        stride *= (uint64_t)a.rm1[j] + 1;
+    }
+    return a;
 }
 
 // *space = prod(hi_j - lo_j + 1) over the nkeys {lo, hi} pairs of b, saturated at 2^63;
@@ -1500,18 +1906,7 @@ int mq_group_by_plan(const int32_t* const* d_keys, int nkeys, const int32_t* d_v
         return MQ_OK;
     }
     g->path = path != MQ_GROUP_AUTO ? path : space <= kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
-    ByArgs a = {};
-    uint64_t stride = 1;  // up to the key space
-    for (int j = nkeys - 1; j >= 0; j--) {
-        a.keys[j] = d_keys[j];
-        a.lo[j] = (uint32_t)b[2 * j];
-        a.rm1[j] = (uint32_t)((int64_t)b[2 * j + 1] - (int64_t)b[2 * j]);
-        a.stride[j] = (uint32_t)stride;
-        g->klo[j] = b[2 * j];
-        g->krm1[j] = a.rm1[j];
-        g->kstride[j] = a.stride[j];
-        stride *= (uint64_t)a.rm1[j] + 1;
-    }
+    const ByArgs a = by_args(g, d_keys, b, nkeys);
     if (g->path == MQ_GROUP_DENSE) {
         g->lo = 0;  // the table is addressed by the code
         g->range = (uint32_t)space;
@@ -1524,6 +1919,165 @@ int mq_group_by_plan(const int32_t* const* d_keys, int nkeys, const int32_t* d_v
         return rc;
     }
     if (h_path) *h_path = g->path;
+    *h_groups = g->groups;
+    *out = g;
+    return MQ_OK;
+}
+
+int mq_group_by_where_plan(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* const* d_keys,
+                           int nkeys, const int32_t* d_vals, uint64_t n, const int32_t* h_key_bounds, int path, mq_group** out,
+                           uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream) {
+    const char* who = "mq_group_by_where_plan";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (out) *out = nullptr;
+    if (h_groups) *h_groups = 0;
+    if (h_rows) *h_rows = 0;
+    if (nkeys < 1 || nkeys > kMaxKeys) return set_err(MQ_EINVAL, "%s: nkeys %d outside 1..%d", who, nkeys, kMaxKeys);
+    if (!out || !h_groups || !d_cols || !h_ranges || (n && (!d_keys || !d_vals))) return set_err(MQ_EINVAL, "%s: NULL pointer", who);
+    if (nkeys == 1)
+        return mq_group_where_plan(d_cols, h_ranges, ncols, d_keys ? d_keys[0] : nullptr, d_vals, n, h_key_bounds, path, out,
+                                   h_groups, h_path, h_rows, stream);
+    if (ncols < 1 || ncols > MQ_WHERE_MAX_COLS)
+        return set_err(MQ_EINVAL, "%s: ncols %d outside 1..%d", who, ncols, (int)MQ_WHERE_MAX_COLS);
+    if (path != MQ_GROUP_AUTO && path != MQ_GROUP_DENSE && path != MQ_GROUP_SORT)
+        return set_err(MQ_EINVAL, "%s: path %d", who, path);
+    if (n >= (1ull << 31)) return set_err(MQ_EINVAL, "%s: n >= 2^31", who);
+    int32_t b[2 * kMaxKeys];
+    uint64_t space = 0;
+    // the bounds given, checked before anything is allocated; bounds the plan finds, after it found them
+    auto check_space = [&]() {
+        if (!by_space(b, nkeys, &space)) return set_err(MQ_EINVAL, "%s: a column's bounds are empty", who);
+        if (space > (1ull << 32))
+            return set_err(MQ_EINVAL, "%s: the key space %llu (saturated at 2^63) is wider than 2^32", who, (u64)space);
+        if (path == MQ_GROUP_DENSE && space > kDenseSlots)
+            return set_err(MQ_EINVAL, "%s: the key space %llu exceeds the dense path's %u slots", who, (u64)space, kDenseSlots);
+        return (int)MQ_OK;
+    };
+    if (n) {
+        for (int c = 0; c < ncols; c++)
+            if (!d_cols[c] || (reinterpret_cast<uintptr_t>(d_cols[c]) & 3u))
+                return set_err(MQ_EINVAL, "%s: column %d NULL or not 4-byte aligned", who, c);
+        for (int j = 0; j < nkeys; j++)
+            if (!d_keys[j] || (reinterpret_cast<uintptr_t>(d_keys[j]) & 3u))
+                return set_err(MQ_EINVAL, "%s: key column %d NULL or not 4-byte aligned", who, j);
+        if (reinterpret_cast<uintptr_t>(d_vals) & 3u) return set_err(MQ_EINVAL, "%s: value column not 4-byte aligned", who);
+        if (h_key_bounds) {
+            for (int j = 0; j < 2 * nkeys; j++) b[j] = h_key_bounds[j];
+            if ((rc = check_space())) return rc;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    WhereArgs w;
+    bool empty, wvec;
+    fold_ranges(d_cols, h_ranges, ncols, &w, &empty, &wvec);
+    mq_group* g = new (std::nothrow) mq_group();
+    if (!g) return set_err(MQ_ENOMEM, "%s: out of host memory", who);
+    g->dev = dev;
+    g->n = n;
+    g->vals = d_vals;
+    g->stream = st;
+    g->nkeys = nkeys;
+    g->path = path == MQ_GROUP_SORT ? MQ_GROUP_SORT : MQ_GROUP_DENSE;  // what a plan without rows reports
+    auto no_groups = [&]() {
+        if (h_path) *h_path = g->path;
+        *out = g;
+        return MQ_OK;
+    };
+    if (n == 0 || empty) return no_groups();
+    auto fail = [&](int code) {
+        release(g, st);
+        return code;
+    };
+    bool kvec = true;
+    for (int j = 0; j < nkeys; j++) kvec = kvec && aligned16(d_keys[j]);
+    uint64_t rows = 0;
+    bool rows_known = false;
+    if (!h_key_bounds) {  // one more pass over the predicates and the key lines that hold a survivor
+        ByArgs ka = {};
+        for (int j = 0; j < nkeys; j++) ka.keys[j] = d_keys[j];
+        uint32_t grid = 0;
+        ByBounds* part = nullptr;
+        auto launch = [&](auto nk) {
+            constexpr int NK = decltype(nk)::value;
+            const bool vec = wvec && kvec;
+            const void* fn = vec ? reinterpret_cast<const void*>(&k_group_by_where_bounds<NK, true>)
+                                 : reinterpret_cast<const void*>(&k_group_by_where_bounds<NK, false>);
+            uint64_t rpb;
+            geometry(s, n, fn, &grid, &rpb, (uint64_t)bw_tiles(NK) * kTileRows);
+            part = static_cast<ByBounds*>(pool_alloc(((size_t)grid + 1) * sizeof(ByBounds)));  // the blocks', then the result
+            if (!part) return set_err(MQ_ENOMEM, "%s: workspace allocation failed", who);
+            if (vec)
+                hipLaunchKernelGGL((k_group_by_where_bounds<NK, true>), dim3(grid), dim3(kTPB), 0, st, w, ka, n, rpb, part);
+            else
+                hipLaunchKernelGGL((k_group_by_where_bounds<NK, false>), dim3(grid), dim3(kTPB), 0, st, w, ka, n, rpb, part);
+            LAUNCHCHK("k_group_by_where_bounds");
+            return (int)MQ_OK;
+        };
+        rc = nkeys == 2   ? launch(std::integral_constant<int, 2>{})
+             : nkeys == 3 ? launch(std::integral_constant<int, 3>{})
+                          : launch(std::integral_constant<int, 4>{});
+        ByBounds found = {};
+        if (!rc) {
+            hipLaunchKernelGGL(k_group_by_where_bounds_fold, dim3(1), dim3(kTPB), 0, st, part, grid, part + grid);
+            if (hipGetLastError() != hipSuccess) rc = set_err(MQ_EHIP, "launch of k_group_by_where_bounds_fold failed");
+        }
+        if (!rc && hipMemcpyAsync(&found, part + grid, sizeof found, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "%s: bounds download failed", who);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+        pool_free(part);
+        if (rc) return fail(rc);
+        if (found.count == 0) return no_groups();
+        for (int j = 0; j < nkeys; j++) {
+            b[2 * j] = found.mn[j];
+            b[2 * j + 1] = found.mx[j];
+        }
+        rows = found.count;
+        rows_known = true;
+        if ((rc = check_space())) return fail(rc);
+    }
+    g->path = path != MQ_GROUP_AUTO ? path : space <= kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
+    const ByArgs a = by_args(g, d_keys, b, nkeys);
+    if (g->path == MQ_GROUP_DENSE) {
+        g->lo = 0;  // the table is addressed by the code
+        g->range = (uint32_t)space;
+        rc = plan_dense(s, g, nullptr, d_vals, n, st, &w, wvec, rows_known || !h_rows ? nullptr : &rows, &a, nkeys);
+        if (rc) return fail(rc);
+    } else {
+        // the K matching rows' positions, their codes packed through them, their values, then the sort path
+        const size_t ws_bytes = mq_where_workspace_bytes(n);
+        void* ws = pool_alloc(ws_bytes);
+        int32_t* pos = static_cast<int32_t*>(pool_alloc(n * 4));
+        u64* d_k = static_cast<u64*>(pool_alloc(sizeof(u64)));
+        u64 k = 0;
+        rc = ws && pos && d_k ? MQ_OK : set_err(MQ_ENOMEM, "%s: allocation failed", who);
+        if (!rc)
+            rc = mq_where_positions(d_cols, h_ranges, ncols, nullptr, n, pos, reinterpret_cast<uint64_t*>(d_k), ws, ws_bytes,
+                                    stream);
+        if (!rc && hipMemcpyAsync(&k, d_k, sizeof k, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "%s: count download failed", who);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+        pool_free(d_k);
+        pool_free(ws);
+        if (!rc && k) {
+            g->own_vals = static_cast<int32_t*>(pool_alloc(k * 4));
+            if (!g->own_vals) rc = set_err(MQ_ENOMEM, "%s: allocation failed", who);
+            if (!rc) rc = mq_fetch(d_vals, pos, k, g->own_vals, stream);
+            if (!rc) {
+                g->vals = g->own_vals;
+                g->n = k;
+                rc = plan_by_sort(s, g, a, nkeys, n, st, who, pos, k);  // synchronises
+            }
+        }
+        pool_free_on(pos, st);  // the gather and the pack queued above are its last readers
+        if (rc) return fail(rc);
+        rows = k;
+    }
+    if (h_path) *h_path = g->path;
+    if (h_rows) *h_rows = rows;
     *h_groups = g->groups;
     *out = g;
     return MQ_OK;

@@ -1339,6 +1339,23 @@ Result** group_aggregate_where(GeneralizedColumn** columns, int** lows, int** hi
     return group_results(who, g, groups, 1, rc, ret_status);
 }
 
+/* The nkeys key columns of group_aggregate_by and group_aggregate_by_where on the calling
+ * device: dk[0 .. nkeys). Every column is *n rows long, where the first one sets *n unless
+ * have_n. 0; positive: a failure that has been reported; -1: an argument of the wrong kind;
+ * -2: different lengths. */
+static int by_keys(GeneralizedColumn** keys, int nkeys, const int32_t** dk, size_t* n, int have_n, Status* st) {
+    if (!keys) return -1;
+    int differ = 0;
+    for (int j = 0; j < nkeys; j++) {
+        size_t m = 0;
+        const int a = keys[j] ? gcol_device(keys[j], &dk[j], &m, st) : -1;
+        if (a) return a;
+        if (j == 0 && !have_n) *n = m;
+        differ = differ || m != *n;
+    }
+    return differ ? -2 : 0;
+}
+
 /* group_aggregate by the tuple of `nkeys` key columns, in lexicographic order (no reference
  * counterpart): nkeys + 4 Results, the key columns (INT) first. No key bounds
  * are passed (group_aggregate's reason): the plan reads every key column once more for them. */
@@ -1352,23 +1369,52 @@ Result** group_aggregate_by(GeneralizedColumn** keys, int nkeys, GeneralizedColu
     const int32_t* dk[MQ_GROUP_MAX_KEYS];
     const int32_t* dv = NULL;
     size_t n = 0, m = 0;
-    int bad = !keys || !values, differ = 0;
-    for (int j = 0; j <= nkeys && !bad; j++) { /* the key columns, then the values */
-        GeneralizedColumn* gc = j < nkeys ? keys[j] : values;
-        const int a = gc ? gcol_device(gc, j < nkeys ? &dk[j] : &dv, &m, ret_status) : -1;
-        if (a > 0) return NULL;
-        bad = a < 0;
-        if (j == 0) n = m;
-        differ = differ || m != n;
+    int a = values ? by_keys(keys, nkeys, dk, &n, 0, ret_status) : -1;
+    if (a > 0) return NULL;
+    if (a != -1) { /* then the values */
+        const int b = gcol_device(values, &dv, &m, ret_status);
+        if (b > 0) return NULL;
+        a = b < 0 ? -1 : a || m != n ? -2 : 0;
     }
-    if (bad || differ) {
+    if (a) {
         dml_fail(ret_status, who,
-                 bad ? "keys and values must each be a Column or an INT Result" : "the keys and values differ in length");
+                 a == -1 ? "keys and values must each be a Column or an INT Result" : "the keys and values differ in length");
         return NULL;
     }
     mq_group* g = NULL;
     uint64_t groups = 0;
     const int rc = mq_group_by_plan(dk, nkeys, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, g_stream);
+    return group_results(who, g, groups, nkeys, rc, ret_status);
+}
+
+/* group_aggregate_by over the rows for which every range holds (no reference counterpart;
+ * DESIGN.md §3.16): what select_where -> fetch_column x (nkeys + 1) -> group_aggregate_by
+ * returns, in one operator. No key bounds are passed (group_aggregate's reason): the plan finds
+ * every key column's range over the matching rows itself. */
+Result** group_aggregate_by_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn** keys,
+                                  int nkeys, GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "group_aggregate_by_where";
+    if (nkeys < 1 || nkeys > MQ_GROUP_MAX_KEYS) {
+        dml_fail(ret_status, who, "nkeys outside 1..4");
+        return NULL;
+    }
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t* dk[MQ_GROUP_MAX_KEYS];
+    const int32_t* dv = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0;
+    if (where_args(who, columns, lows, highs, ncols, values, d_cols, ranges, &dv, &n, ret_status)) return NULL;
+    const int a = by_keys(keys, nkeys, dk, &n, 1, ret_status);
+    if (a > 0) return NULL;
+    if (a) {
+        dml_fail(ret_status, who, a == -1 ? "every key must be a Column or an INT Result" : "the columns and keys differ in length");
+        return NULL;
+    }
+    mq_group* g = NULL;
+    uint64_t groups = 0;
+    const int rc = mq_group_by_where_plan(d_cols, ranges, ncols, dk, nkeys, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, NULL,
+                                          g_stream);
     return group_results(who, g, groups, nkeys, rc, ret_status);
 }
 

@@ -201,6 +201,9 @@ _SIGS = {
     "mq_group_by_plan": (_int, [C.POINTER(_vp), _int, _vp, _u64, C.POINTER(_i32), _int, C.POINTER(_vp), C.POINTER(_u64),
                                 C.POINTER(_int), _vp]),
     "mq_group_by_write": (_int, [_vp, C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
+    "mq_group_by_where_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, C.POINTER(_vp), _int, _vp, _u64,
+                                      C.POINTER(_i32), _int, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_int),
+                                      C.POINTER(_u64), _vp]),
     "mq_topk_default_cap": (_u64, []),
     "mq_topk_auto_path": (_int, [_u64, _u64, _u64]),
     "mq_topk": (_int, [_vp, _vp, _u64, _u64, _int, _int, _u64, _vp, _vp, C.POINTER(MqTopkInfo), _vp]),
@@ -260,6 +263,10 @@ _SIGS = {
                                                C.POINTER(GeneralizedColumn), _PS]),
     "group_aggregate_by": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), _int, C.POINTER(GeneralizedColumn),
                                             _PS]),
+    "group_aggregate_by_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                                                  C.POINTER(C.POINTER(_int)), _int,
+                                                  C.POINTER(C.POINTER(GeneralizedColumn)), _int,
+                                                  C.POINTER(GeneralizedColumn), _PS]),
     "log_result": (None, [_PR]),
     "should_use_index": (C.c_bool, [C.POINTER(Column), _int, _int]),
     # load path (db_manager.h:254)

@@ -491,6 +491,60 @@ int mq_group_by_write(mq_group* g, int32_t* const* d_keys_out /* NULL, or host a
                       pointers, any of them NULL */, uint64_t* d_count_out, int64_t* d_sum_out,
                       int32_t* d_min_out, int32_t* d_max_out, void* stream);
 
+/* ---- GROUP BY over two to four key columns under a WHERE ----
+ * SELECT k0, k1, .., count(*), sum(v), min(v), max(v) WHERE c0 IN [..) AND .. GROUP BY k0, k1, ..
+ * in one operator. With m[i] = every one of the ncols ranges holds for row i
+ * (mq_group_where_plan's predicates), the result is exactly that of mq_group_by_plan over the
+ * key columns and the values restricted to m; bitwise the same whatever the path, the grid, the
+ * alignment, the order of the predicates or the order in which blocks finish. The handle is an
+ * ordinary mq_group with nkeys > 1, served by mq_group_by_write and mq_group_free. *h_rows (may
+ * be NULL) = the matching rows. Any of the pointers may be the same column, a key a predicate
+ * column and the values a key among them. nkeys == 1 is mq_group_where_plan itself (the call is
+ * handed on).
+ * h_key_bounds (NULL or {lo_0, hi_0, lo_1, hi_1, ..}, inclusive) constrains the components of
+ *        MATCHING rows only: a component of a row that fails a predicate is never an error and
+ *        never an address. Every component of a matching row is checked against its own
+ *        column's bounds (mq_group_by_plan's rule: (3, 12) under ranges (10, 10) fails though its
+ *        summed code lies inside the table). NULL costs one more pass, k_group_by_where_bounds:
+ *        the predicates and the surviving key lines of all nkeys columns at once give every
+ *        column's min and max over the matching rows and their number. P = prod(hi_j - lo_j + 1)
+ *        picks the path as in mq_group_by_plan (mq_group_by_auto_path says which).
+ * dense (P <= mq_group_dense_slots()): one streaming pass, k_group_by_where_dense: the predicate
+ *        columns as mq_where_agg reads them, then of the nkeys key columns and the value column
+ *        only the 128-byte lines in which a row survived, the tuple's code as the slot of
+ *        mq_group_plan's per-block LDS tables.
+ * sort  (P <= 2^32): mq_where_positions, then k_group_by_pack_pos writes code ^ 0x80000000 of
+ *        the K matching rows straight from the key columns through the positions (no key column
+ *        is gathered), the values are gathered (mq_fetch) into a buffer the handle owns, and
+ *        mq_group_plan's sort path runs on the packed column.
+ * Measured at 1e9 rows (nkeys 2 and 4 over 2025 tuples, a leading predicate
+ * that passes 0.1-100 % of its column and a second one that passes half) against
+ * mq_where_positions -> mq_fetch x (nkeys + 1) -> mq_group_by_plan with the same bounds: with
+ * bounds given, behind a uniform leading column 0.81-0.87 of the chain's time at 0.1 %, a tie
+ * at 1 % (1.01-1.04), 0.68-0.69 at 10 %, 0.48-0.51 at 50 % and 0.36-0.39 at 100 %; behind a
+ * clustered one 0.91-0.98 at 10 %, 0.35-0.45 from 50 % upward and a loss at 0.1-1 % (1.48-1.72;
+ * a few blocks do every table update); with NULL bounds a win from 50 % upward (0.59-0.86) and
+ * a loss below (1.21-1.63 uniform, 1.32-2.58 clustered). Every range unbounded runs 0-3 %
+ * behind mq_group_by_plan. The sort path with 1e8 matching rows in 6.3e7 groups: 0.90-0.94 of
+ * the chain. Nothing is dispatched differently by selectivity.
+ * Synchronises; takes its scratch from the library's pool. n == 0, a range that no int32
+ * satisfies (no column is read) or no matching row give MQ_OK, zero groups and a handle to
+ * free. d_vals must stay valid until the write has run (dense path).
+ * MQ_EINVAL, with *out = NULL, *h_groups = 0, *h_rows = 0 and nothing allocated: ncols outside
+ * 1..8, nkeys outside 1..4, n >= 2^31, a NULL d_cols, h_ranges, d_keys, out or h_groups, a NULL
+ * or not 4-byte aligned column, key or value pointer with n > 0, a path that is none of the
+ * three, and of given bounds with n > 0 lo_j > hi_j, P > 2^32, MQ_GROUP_DENSE forced on
+ * P > mq_group_dense_slots(); with everything released: a matching row with a component outside
+ * its column's given bounds, and P > 2^32 or a forced MQ_GROUP_DENSE past the slots for the
+ * bounds the plan found. */
+int mq_group_by_where_plan(const int32_t* const* d_cols /* host array of ncols device pointers */,
+                           const struct mq_range* h_ranges, int ncols,
+                           const int32_t* const* d_keys /* host array of nkeys device pointers */, int nkeys,
+                           const int32_t* d_vals, uint64_t n,
+                           const int32_t* h_key_bounds /* NULL or 2*nkeys host ints */, int path,
+                           mq_group** out, uint64_t* h_groups, int* h_path /* may be NULL */,
+                           uint64_t* h_rows /* matching rows; may be NULL */, void* stream);
+
 /* ---- top k: the k smallest or largest rows, in order ----
  * n < 2^31 int32 values d_vals[i] with an optional int32 payload d_payload[i] (a positions
  * vector, the pair select_result takes; NULL: the payload is the row id i). The output is

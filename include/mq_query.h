@@ -365,6 +365,28 @@ Result** group_aggregate_where(GeneralizedColumn** columns, int** lows, int** hi
  * key space (the product of the columns' ranges) wider than 2^32. */
 Result** group_aggregate_by(GeneralizedColumn** keys, int nkeys, GeneralizedColumn* values, Status* ret_status);
 
+/* ---- GROUP BY over several key columns under a WHERE (not in the reference) ----
+ * group_aggregate_by_where: SELECT k0, .., count(*), sum(v), min(v), max(v) FROM t WHERE c0 IN
+ * [..) AND c1 IN [..) ... GROUP BY k0, .. in one operator (DESIGN.md §3.16;
+ * mq_group_by_where_plan in mq_device.h): what select_where -> fetch_column x (nkeys + 1) ->
+ * group_aggregate_by returns, without the positions, the fetched columns and the host round
+ * trips between them. `columns`, `lows`, `highs` and `ncols` are group_aggregate_where's;
+ * `keys`, `nkeys` and `values` are group_aggregate_by's, all as long as the predicate columns,
+ * any of them the same object. Returns group_aggregate_by's nkeys + 4 Results under its
+ * ownership and shadow rules: one tuple per distinct (k0, .., k_{nkeys-1}) that has a matching
+ * row. No matching row gives nkeys + 4 empty Results and OK. No key bounds are passed, for
+ * group_aggregate's reason: one more pass over the predicates and the surviving key lines
+ * finds every key column's range over the matching rows, so a filter that narrows the tuples
+ * to mq_group_dense_slots() takes the dense path. Measured on the device at 1e9 rows, the
+ * plan as called here (no bounds) beats mq_where_positions -> mq_fetch x (nkeys + 1) ->
+ * mq_group_by_plan when the leading predicate passes half of the rows or more (0.59-0.86 of its
+ * time) and loses below (1.2-2.6). Put the most selective predicate first. Runs on the calling device; a column held as row shards drops them and is split again
+ * on next use. ERROR and NULL (a "libmq:" line on stderr): group_aggregate_where's and
+ * group_aggregate_by's cases. */
+Result** group_aggregate_by_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
+                                  GeneralizedColumn** keys, int nkeys, GeneralizedColumn* values,
+                                  Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
