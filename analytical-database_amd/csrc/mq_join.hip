@@ -1161,6 +1161,7 @@ int mq_join_probe(mq_join* j, const int32_t* d_c2, uint64_t n2, uint64_t* h_m, v
     release_probe(j, st);
     j->pr.n2 = n2;
     j->pr.m = 0;
+    j->pr.longcap = 0;
     *h_m = 0;
     if (n2 == 0 || j->n1 == 0) return MQ_OK;
     // a partitioned build and a probe side too small to pay for its own partition (its
@@ -1287,6 +1288,7 @@ int mq_join_write(mq_join* j, const int32_t* d_p2, int32_t* d_out1, int32_t* d_o
     if (qcap > 0xFFFFFFF0ull) return set_err(MQ_EINVAL, "mq_join_write: %llu pairs", (unsigned long long)j->pr.m);
     pool_free_on(j->pr.longq, (hipStream_t)stream);
     if (!(j->pr.longq = (u64*)pool_alloc(qcap * 8 + 16))) return set_err(MQ_ENOMEM, "mq_join_write: long-run list");
+    j->pr.longcap = qcap;
     uint32_t* const nlong = reinterpret_cast<uint32_t*>(j->pr.longq + qcap);
     HIPCHK(hipMemsetAsync(nlong, 0, 4, (hipStream_t)stream));
     hipLaunchKernelGGL(k_join_write, dim3(stream_grid(s, j->pr.n2)), dim3(kTPB), 0, (hipStream_t)stream,
@@ -1317,6 +1319,22 @@ int mq_join_counts(mq_join* j, uint32_t* d_cnt, void* stream) {
     const uint32_t* plen = (!hits && !j->pr.pruns) ? j->pr.plen : nullptr;
     hipLaunchKernelGGL(k_join_counts, dim3(stream_grid(s, j->pr.n2)), dim3(kTPB), 0, st, hits, pk, plen, j->pr.n2, d_cnt);
     LAUNCHCHK("k_join_counts");
+    return MQ_OK;
+}
+
+int mq_join_state(const mq_join* j, uint32_t* out) {
+    if (!j || !out) return set_err(MQ_EINVAL, "mq_join_state: NULL pointer");
+    const mqj::ProbeState& p = j->pr;
+    out[0] = (uint32_t)j->unique;
+    out[1] = (j->part ? MQ_JOIN_STATE_PART : 0u) | (j->dupw ? MQ_JOIN_STATE_DUPW : 0u) |
+             (j->packed ? MQ_JOIN_STATE_PACKED : 0u) | (j->rs ? MQ_JOIN_STATE_RS : 0u) |
+             (p.pruns ? MQ_JOIN_STATE_PRUNS : 0u) | (p.run2 ? MQ_JOIN_STATE_RUN2 : 0u) |
+             (p.deferred ? MQ_JOIN_STATE_DEFERRED : 0u) | (p.longcap ? MQ_JOIN_STATE_ROW_WRITE : 0u);
+    out[2] = 0;
+    if (p.longcap) {  // the entry count k_join_write left behind the list
+        HIPCHK(hipStreamSynchronize(j->stream));
+        HIPCHK(hipMemcpy(&out[2], p.longq + p.longcap, 4, hipMemcpyDeviceToHost));
+    }
     return MQ_OK;
 }
 

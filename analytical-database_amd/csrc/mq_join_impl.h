@@ -115,6 +115,8 @@ struct ProbeState {
     u64* offs;
     u64* scan_scratch;
     u64* longq;            // per-row write: chunks of the long runs (k_join_write_long)
+    uint64_t longcap;      // ... its capacity (the entry count follows it); 0: no per-row write
+                           // since the last probe (mq_join_state)
     // deferred (round 6): the partitioned probe stopped before its last inverse pass, which
     // mq_join_write runs fused with the pair write (dmode: 0 unique u32 results, 1 unique
     // u64, 2 run2 records); dperm = pass 0's places of the probe rows (pool, owned),

@@ -28,6 +28,9 @@ MQ_GROUP_MAX_KEYS = 4
 MQ_TOPK_AUTO, MQ_TOPK_SELECT, MQ_TOPK_SORT = 0, 1, 2
 MQ_TOPK_SORT_DIV = 4
 MQ_WHERE_MAX_COLS = 8
+MQ_JOIN_STATE_WORDS = 3  # include/mq_device.h mq_join_state
+(MQ_JOIN_STATE_PART, MQ_JOIN_STATE_DUPW, MQ_JOIN_STATE_PACKED, MQ_JOIN_STATE_RS, MQ_JOIN_STATE_PRUNS,
+ MQ_JOIN_STATE_RUN2, MQ_JOIN_STATE_DEFERRED, MQ_JOIN_STATE_ROW_WRITE) = (1 << b for b in range(8))
 
 
 class MqAgg(C.Structure):
@@ -139,6 +142,7 @@ _SIGS = {
     "mq_group_sort_geometry": (None, [_u64, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
     "mq_dml_geometry": (None, [_u64, C.POINTER(C.c_uint32), C.POINTER(_u64), C.POINTER(C.c_uint32), C.POINTER(_u64)]),
     "mq_test_set_cu_limit": (_int, [_int]),
+    "mq_join_state": (_int, [_vp, C.POINTER(C.c_uint32)]),
     # data
     "mq_gen_uniform": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "mq_gen_join_keys": (_int, [_vp, _u64, _int, _vp]),

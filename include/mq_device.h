@@ -124,6 +124,27 @@ void mq_dml_geometry(uint64_t n, uint32_t* prefix_blocks, uint64_t* prefix_chunk
  * sizes that depend on the grid (mq_shared_select_workspace_bytes) are queried after
  * the call. Off by default, and no environment variable sets it. */
 int mq_test_set_cu_limit(int cus);
+/* Test hook: what a join handle (mq_join_build below) and its last probe and write are in,
+ * so that a test can assert the path it means to compare before it compares. Host only:
+ * it launches no kernel and changes nothing; with MQ_JOIN_STATE_ROW_WRITE set it waits for
+ * the handle's stream and reads one word back. out (host, MQ_JOIN_STATE_WORDS u32):
+ *   out[0]  the build's form: 1 = the unique table {key, build position}; 2 = a runs table
+ *           (distinct keys -> run) or the partitioned words answering duplicate keys;
+ *           0 = the global-CAS table of run heads;
+ *   out[1]  MQ_JOIN_STATE_* flags;
+ *   out[2]  with MQ_JOIN_STATE_ROW_WRITE: the entries (one per 65 536-pair chunk of a run
+ *           of more than 4096 pairs) the last write listed for k_join_write_long; else 0. */
+#define MQ_JOIN_STATE_WORDS 3
+#define MQ_JOIN_STATE_PART 1u       /* the build kept its window partition (no global table) */
+#define MQ_JOIN_STATE_DUPW 2u       /* ... and answers duplicate keys window by window */
+#define MQ_JOIN_STATE_PACKED 4u     /* runs table: payloads are start << 4 | length */
+#define MQ_JOIN_STATE_RS 8u         /* runs table over the sorted build (run bounds kept) */
+#define MQ_JOIN_STATE_PRUNS 16u     /* last probe: a packed run per row, lengths per 64 rows */
+#define MQ_JOIN_STATE_RUN2 32u      /* last probe: short runs' build positions per row */
+#define MQ_JOIN_STATE_DEFERRED 64u  /* last probe: its last inverse pass is still to run */
+#define MQ_JOIN_STATE_ROW_WRITE 128u /* the last write since that probe was the per-row one */
+struct mq_join;
+int mq_join_state(const struct mq_join* join, uint32_t* out);
 
 /* ---- synthetic data (bench/tests; SURVEY.md §8(c) generator) ---- */
 /* out[i] = (int32)(sm64(seed*0x100000001B3 + i) % modulus) */

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from devbuf import Dev
+from joincases import ORACLE_CASES, oracle_inputs
 from refapi import Api, make_column, mq, take
 
 pytestmark = pytest.mark.gpu
@@ -657,9 +658,7 @@ JOIN_PATHS = {"winruns": {}, "sorted": {"MQ_JOIN_WINRUNS": "0"},
 
 
 @pytest.mark.parametrize("path", list(JOIN_PATHS))
-@pytest.mark.parametrize("case", ["unique", "dups", "skew", "neg", "tiny", "empty", "marker",
-                                  "unique_partitioned", "dups_partitioned",
-                                  "ragged_hits", "dups_short_runs", "dups_run_of_15"])
+@pytest.mark.parametrize("case", ORACLE_CASES)
 def test_hash_join_vs_oracle(lib, refcpu, monkeypatch, case, path):
     """Duplicate keys: winruns (default) partitions the build rows by window and finds
     each window's runs in LDS (k_win_build_runs); a window over 6144 rows or 3072 keys,
@@ -669,55 +668,7 @@ def test_hash_join_vs_oracle(lib, refcpu, monkeypatch, case, path):
     for k, v in JOIN_PATHS[path].items():
         monkeypatch.setenv(k, v)
     rng = np.random.default_rng(hash(case) % 1000)
-    if case == "unique":
-        c1 = rng.permutation(200_000).astype(np.int32)
-        c2 = rng.integers(0, 400_000, 150_000, dtype=np.int32)
-    elif case == "dups":
-        c1 = rng.integers(0, 5000, 100_000, dtype=np.int32)
-        c2 = rng.integers(0, 6000, 30_000, dtype=np.int32)
-    elif case == "skew":  # one huge group plus a long tail
-        c1 = np.where(rng.random(50_000) < 0.5, 7, rng.integers(0, 10 ** 6, 50_000)).astype(np.int32)
-        c2 = np.concatenate([[7, 7, 3], rng.integers(0, 10 ** 6, 2000)]).astype(np.int32)
-    elif case == "neg":
-        c1 = rng.integers(-(2 ** 31), 2 ** 31 - 1, 20_000, dtype=np.int64).astype(np.int32)
-        c1[:4] = [-(2 ** 31), 2 ** 31 - 1, 0, -1]
-        c2 = np.concatenate([c1[::3], rng.integers(-100, 100, 500)]).astype(np.int32)
-    elif case == "tiny":  # the reference's full-table hang shapes (multimap.c:65-71)
-        c1 = np.array([5, 9], dtype=np.int32)
-        c2 = np.array([1, 9, 5, 5, 2], dtype=np.int32)
-    elif case == "marker":  # unique keys, one build row {key -1, position -1} = the
-        c1 = (rng.permutation(3000) - 1500).astype(np.int32)  # packed table's empty word
-        c2 = rng.integers(-1600, 1600, 5000, dtype=np.int32)
-    elif case == "ragged_hits":  # unique keys, probe rows 64k+1 with hits at the word edges
-        c1 = rng.permutation(1000).astype(np.int32)
-        c2 = np.concatenate([np.arange(129), rng.integers(500, 2000, 64 * 7 + 1), [999]]).astype(np.int32)
-    elif case == "dups_short_runs":  # > 2^16 rows, runs of 1..14 rows in input order
-        # (spread keys: the oracle's `key % size` multimap goes quadratic on dense ones)
-        keys = rng.choice(1 << 30, 90_000, replace=False).astype(np.int32)
-        c1 = np.repeat(keys[:60_000], rng.integers(1, 15, 60_000))[:300_000]
-        c1 = c1[rng.permutation(len(c1))]
-        c2 = np.concatenate([rng.choice(keys[:60_000], 100_000), keys[60_000:80_000]]).astype(np.int32)
-    elif case == "dups_run_of_15":  # one key on 15 rows: not packable, the window flags
-        keys = rng.choice(1 << 30, 250_000, replace=False).astype(np.int32)
-        c1 = keys[:200_000].copy()
-        c1[1 + rng.choice(len(c1) - 1, 14, replace=False)] = c1[0]
-        c2 = rng.choice(keys, 100_000)
-        c2[:5] = c1[0]
-    elif case in ("unique_partitioned", "dups_partitioned"):
-        # > 2^22 build rows: the window-partitioned insert. Keys from the spread
-        # config-5 generator: the oracle restates the reference's `key % size`
-        # multimap, which goes quadratic on dense or arithmetic key runs.
-        c1 = rng.permutation(refcpu.gen_join(5_000_000, "build"))
-        c2 = refcpu.gen_join(3_000_000, "probe")
-        if case == "dups_partitioned":  # one duplicate, seen only after partitioning
-            c1[4_999_999] = c1[17]
-    else:
-        c1 = np.array([], dtype=np.int32)
-        c2 = np.array([1, 2], dtype=np.int32)
-    p1 = rng.integers(0, 10 ** 7, len(c1), dtype=np.int32)
-    p2 = rng.integers(0, 10 ** 7, len(c2), dtype=np.int32)
-    if case == "marker":
-        p1[np.nonzero(c1 == -1)[0][0]] = -1
+    c1, p1, c2, p2 = oracle_inputs(case, rng, refcpu.gen_join)  # (the builders: joincases.py)
     g1, g2 = _dev_join(lib, c1, p1, c2, p2)
     w1, w2 = refcpu.hash_join(c1, p1, c2, p2)
     assert np.array_equal(g1, w1) and np.array_equal(g2, w2), case

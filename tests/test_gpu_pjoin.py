@@ -24,6 +24,7 @@ import sys
 import numpy as np
 import pytest
 
+import joincases
 from devbuf import Dev
 from refapi import _libc, make_column, make_result, mq, take
 from test_pjoin_dist import HostPhases, bucket
@@ -193,7 +194,7 @@ def test_shard_join_injected_failure_then_goldens(lib, refcpu, goldens, g, phase
         assert (len(a1), f"{refcpu.fnv1a64_pairs(a1, a2):016x}") == (r["m"], r["pairs_fnv1a64"]), dup
 
 
-CASES = ["unique", "dups", "skew", "neg", "tiny", "empty_build", "empty_probe", "dups_long", "unique_big"]
+CASES = ["unique", "dups", "skew", "neg", "tiny", "empty_build", "empty_probe", "dups_long", "unique_big", "hot_keys"]
 
 
 @pytest.mark.parametrize("g", [2, 3])
@@ -228,14 +229,18 @@ def test_shard_join_vs_oracle(lib, refcpu, monkeypatch, g, case):
         c1 = np.concatenate([keys[:80_000], np.full(6000, keys[5], np.int32)])
         c1 = c1[rng.permutation(len(c1))]
         c2 = np.concatenate([[keys[5]] * 3, rng.choice(keys, 50_000)]).astype(np.int32)
+    elif case == "hot_keys":  # runs of 4096 .. 131 073 rows: mq_join_counts, the exchange and the
+        c1, p1, c2, p2, _ = joincases.hot_keys()  # place on lengths past one 65 536-pair chunk
     else:  # > 2^22 build rows per side in all: the windowed builds on each device
         c1 = rng.permutation(refcpu.gen_join(5_000_000, "build"))
         c2 = refcpu.gen_join(3_000_000, "probe")
-    p1 = rng.integers(0, 10 ** 7, len(c1), dtype=np.int32)
-    p2 = rng.integers(0, 10 ** 7, len(c2), dtype=np.int32)
+    if case != "hot_keys":
+        p1 = rng.integers(0, 10 ** 7, len(c1), dtype=np.int32)
+        p2 = rng.integers(0, 10 ** 7, len(c2), dtype=np.int32)
     D = [Dev.of(x) for x in (c1, p1, c2, p2)]
     g1, g2, _ = shard_join(lib, g, D, len(c1), len(c2), seed=len(c1))
-    w1, w2 = refcpu.hash_join(c1, p1, c2, p2)
+    # (hot_keys: the numpy model, pinned to the oracle on this input by test_join_host.py)
+    w1, w2 = joincases.join_pairs(c1, p1, c2, p2) if case == "hot_keys" else refcpu.hash_join(c1, p1, c2, p2)
     assert np.array_equal(g1, w1) and np.array_equal(g2, w2), case
 
 
