@@ -1211,16 +1211,17 @@ Result** top_k(GeneralizedColumn* values, Result* positions, size_t k, bool desc
 }
 
 /* The arguments select_where and aggregate_where share, resolved on the calling device:
- * ncols columns (and `values`, when given) of one length *n, the bounds as mq_ranges, and
- * the operator's workspace. 0, or nonzero with the failure reported. */
-static int where_args(const char* who, GeneralizedColumn** columns, int** lows, int** highs, int ncols,
-                      GeneralizedColumn* values, const int32_t** d_cols, mq_range* ranges, const int32_t** d_val,
-                      size_t* n, Status* st) {
-    if (ncols < 1 || ncols > MQ_WHERE_MAX_COLS) {
-        dml_fail(st, who, "ncols must be 1..8");
+ * ncols (min_cols .. 8) columns (and `values`, when given) of one length *n (have_n: the
+ * caller's; otherwise the first column's), the bounds as mq_ranges, and the operator's
+ * workspace. 0, or nonzero with the failure reported. */
+static int where_args_from(const char* who, int min_cols, int have_n, GeneralizedColumn** columns, int** lows, int** highs,
+                           int ncols, GeneralizedColumn* values, const int32_t** d_cols, mq_range* ranges,
+                           const int32_t** d_val, size_t* n, Status* st) {
+    if (ncols < min_cols || ncols > MQ_WHERE_MAX_COLS) {
+        dml_fail(st, who, min_cols ? "ncols must be 1..8" : "ncols must be 0..8");
         return -1;
     }
-    int bad = !columns || !lows || !highs || (d_val && !values);
+    int bad = (ncols && (!columns || !lows || !highs)) || (d_val && !values);
     for (int c = 0; c < ncols && !bad; c++) bad = !columns[c];
     int differ = 0;
     for (int c = 0; c <= ncols && !bad; c++) {
@@ -1229,8 +1230,8 @@ static int where_args(const char* who, GeneralizedColumn** columns, int** lows, 
         const int a = gcol_device(c < ncols ? columns[c] : values, c < ncols ? &d_cols[c] : d_val, &rows, st);
         if (a > 0) return -1;
         bad = a < 0;
-        if (c == 0) *n = rows;
-        differ |= rows != *n;
+        if (c == 0 && !have_n) *n = rows;
+        differ |= !bad && rows != *n;
     }
     if (bad || differ) {
         dml_fail(st, who, bad ? "every column must be a Column or an INT Result" : "the columns differ in length");
@@ -1246,6 +1247,12 @@ static int where_args(const char* who, GeneralizedColumn** columns, int** lows, 
     const int rc = grow(&g_ws, &g_ws_bytes, mq_where_workspace_bytes(*n));
     if (rc) return fail(st, "workspace allocation", rc);
     return 0;
+}
+
+static int where_args(const char* who, GeneralizedColumn** columns, int** lows, int** highs, int ncols,
+                      GeneralizedColumn* values, const int32_t** d_cols, mq_range* ranges, const int32_t** d_val,
+                      size_t* n, Status* st) {
+    return where_args_from(who, 1, 0, columns, lows, highs, ncols, values, d_cols, ranges, d_val, n, st);
 }
 
 /* WHERE c0 IN [..) AND c1 IN [..) ...: the positions (or `positions` entries) of the rows
@@ -1279,6 +1286,26 @@ Result* select_where(GeneralizedColumn** columns, int** lows, int** highs, int n
     return int_result_from_device(g_scratch, (size_t)k, ret_status);
 }
 
+/* aggregate_where's four one-tuple Results from an aggregate: count LONG, sum LONG, min INT,
+ * max INT. */
+static Result** agg_results(const mq_agg* a, Status* ret_status) {
+    long* cnt = (long*)malloc(sizeof(long));
+    long* sm = (long*)malloc(sizeof(long));
+    int* mn = (int*)malloc(sizeof(int));
+    int* mx = (int*)malloc(sizeof(int));
+    *cnt = (long)a->count;
+    *sm = (long)a->sum;
+    *mn = a->min;
+    *mx = a->max;
+    Result** out = (Result**)calloc(4, sizeof(Result*));
+    out[0] = new_result(LONG, 1, cnt);
+    out[1] = new_result(LONG, 1, sm);
+    out[2] = new_result(INT, 1, mn);
+    out[3] = new_result(INT, 1, mx);
+    ret_status->code = OK;
+    return out;
+}
+
 /* count, sum, min and max of `values` over the rows for which every range holds (DESIGN.md
  * §3.13): four one-tuple Results, count LONG, sum LONG, min INT, max INT. */
 Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn* values,
@@ -1296,20 +1323,101 @@ Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, i
     }
     mq_agg a;
     if (read_agg(&a, ret_status)) return NULL;
-    long* cnt = (long*)malloc(sizeof(long));
-    long* sm = (long*)malloc(sizeof(long));
-    int* mn = (int*)malloc(sizeof(int));
-    int* mx = (int*)malloc(sizeof(int));
-    *cnt = (long)a.count;
-    *sm = (long)a.sum;
-    *mn = a.min;
-    *mx = a.max;
-    Result** out = (Result**)calloc(4, sizeof(Result*));
-    out[0] = new_result(LONG, 1, cnt);
-    out[1] = new_result(LONG, 1, sm);
-    out[2] = new_result(INT, 1, mn);
-    out[3] = new_result(INT, 1, mx);
-    ret_status->code = OK;
+    return agg_results(&a, ret_status);
+}
+
+/* The key set of select_where_in / aggregate_where_in from `set_keys` (a Column or an INT
+ * Result of any length) on the calling device; the build synchronises g_stream. 0, or nonzero
+ * with the failure reported. */
+static int in_keyset(const char* who, GeneralizedColumn* set_keys, mq_keyset** ks, Status* st) {
+    const int32_t* ds = NULL;
+    size_t ns = 0;
+    const int a = set_keys ? gcol_device(set_keys, &ds, &ns, st) : -1;
+    if (a > 0) return -1;
+    if (a < 0 || ns >= ((size_t)1 << 31)) {
+        dml_fail(st, who, a < 0 ? "set_keys must be a Column or an INT Result" : "2^31 set keys or more");
+        return -1;
+    }
+    const int rc = mq_keyset_build(ds, ns, 0, 0, 0, ks, NULL, g_stream);
+    return rc ? fail(st, who, rc) : 0;
+}
+
+/* The rows behind `keys`, which set the length *n of every other column. */
+static int in_keys(const char* who, GeneralizedColumn* keys, const int32_t** dk, size_t* n, Status* st) {
+    const int a = keys ? gcol_device(keys, dk, n, st) : -1;
+    if (a > 0) return -1;
+    if (a < 0) dml_fail(st, who, "keys must be a Column or an INT Result");
+    return a;
+}
+
+/* WHERE c0 IN [..) AND .. AND k [NOT] IN (set_keys): select_where with a semi (anti: an anti)
+ * join behind the ranges, in one pass (no reference counterpart). The key set
+ * is built per call and freed before returning. */
+Result* select_where_in(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn* keys,
+                        GeneralizedColumn* set_keys, bool anti, Result* positions, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "select_where_in";
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t *dp = NULL, *dk = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0;
+    mq_keyset* ks = NULL;
+    if (in_keyset(who, set_keys, &ks, ret_status)) return NULL;
+    Result* out = NULL;
+    if (in_keys(who, keys, &dk, &n, ret_status) ||
+        where_args_from(who, 0, 1, columns, lows, highs, ncols, NULL, d_cols, ranges, NULL, &n, ret_status))
+        goto done;
+    if (positions) {
+        const int bad = positions->data_type != INT || (positions->num_tuples && !positions->payload);
+        if (bad || positions->num_tuples != n) {
+            dml_fail(ret_status, who, bad ? "positions must be NULL or an INT Result" : "the columns and positions differ in length");
+            goto done;
+        }
+        if (result_device(positions, &dp, ret_status)) goto done;
+    }
+    const int rc = mq_semi_positions(d_cols, ranges, ncols, dk, ks, anti, MQ_SEMI_AUTO, dp, n, (int32_t*)g_scratch,
+                                     (uint64_t*)g_small, g_ws, g_ws_bytes, g_stream);
+    if (rc) {
+        fail(ret_status, who, rc);
+        goto done;
+    }
+    uint64_t k;
+    if (read_count(&k, ret_status)) goto done; /* synchronises: the probe is done with the set */
+    out = int_result_from_device(g_scratch, (size_t)k, ret_status);
+done:
+    mq_stream_sync(g_stream);
+    mq_keyset_free(ks);
+    return out;
+}
+
+/* count, sum, min and max of `values` over the rows select_where_in returns: aggregate_where's
+ * four one-tuple Results. */
+Result** aggregate_where_in(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn* keys,
+                            GeneralizedColumn* set_keys, bool anti, GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "aggregate_where_in";
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t *dv = NULL, *dk = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0;
+    mq_keyset* ks = NULL;
+    if (in_keyset(who, set_keys, &ks, ret_status)) return NULL;
+    Result** out = NULL;
+    mq_agg a;
+    if (in_keys(who, keys, &dk, &n, ret_status) ||
+        where_args_from(who, 0, 1, columns, lows, highs, ncols, values, d_cols, ranges, &dv, &n, ret_status))
+        goto done;
+    const int rc = mq_semi_agg(d_cols, ranges, ncols, dk, ks, anti, MQ_SEMI_AUTO, dv, n, (mq_agg*)g_small, g_ws, g_ws_bytes,
+                               g_stream);
+    if (rc) {
+        fail(ret_status, who, rc);
+        goto done;
+    }
+    if (read_agg(&a, ret_status)) goto done;
+    out = agg_results(&a, ret_status);
+done:
+    mq_stream_sync(g_stream);
+    mq_keyset_free(ks);
     return out;
 }
 

@@ -33,6 +33,10 @@
 //                    that LDS index and output address agree modulo 16 bytes, and leave as
 //                    dwordx4 stores (k_dml_compact's shape).
 // No kernel waits for another block.
+//
+// mq_semi_positions / mq_semi_agg put a key [NOT] IN set predicate behind
+// the ranges in the same stream: k_semi_mask and k_semi_agg, further down, with the scan and
+// k_where_expand shared.
 
 #include <hip/hip_runtime.h>
 
@@ -227,6 +231,191 @@ __global__ __launch_bounds__(kTPB, 8) void k_where_agg(WhereArgs a, const int32_
     }
 }
 
+// ---- ranges AND key [NOT] IN set (mq_semi_positions, mq_semi_agg) ----
+// The key column is read as "the next column" behind the ranges: only the 128-byte lines in
+// which a row survived are requested, the set (mq_keyset.hip: one bit per value of its span)
+// is looked up for surviving rows only, and live &= hit (anti: ~hit). All lookups of an
+// iteration are issued before the first is used. LDSSET: the block first copies the whole
+// bitmap into dynamic LDS (coalesced dwordx4; the bitmap is 16-byte padded) and looks up
+// there; otherwise the bit's word is a plain cached load, so that the bitmap stays in L2 and
+// the Infinity Cache while the columns pass by non-temporally.
+
+extern __shared__ __attribute__((aligned(16))) uint32_t s_semi_set[];
+
+template <bool LDSSET>
+__device__ __forceinline__ void semi_stage(const SemiArgs& k) {
+    if constexpr (LDSSET) {
+        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(k.bits);
+        uint4* dst = reinterpret_cast<uint4*>(s_semi_set);
+        for (uint32_t i = threadIdx.x; i < k.vec16; i += kTPB) dst[i] = src[i];
+        __syncthreads();
+    }
+}
+
+template <bool LDSSET>
+__device__ __forceinline__ uint32_t semi_word(const SemiArgs& k, uint32_t w) {
+    if constexpr (LDSSET) {
+        return s_semi_set[w];
+    } else {
+        return k.bits[w];
+    }
+}
+
+// The set's words for the lane's surviving rows (0 for a dead row or a key outside the span).
+template <bool LDSSET>
+__device__ __forceinline__ void semi_words(const SemiArgs& k, int4 v, uint32_t live, uint32_t (&w)[4]) {
+    const uint32_t d0 = (uint32_t)v.x - k.lo, d1 = (uint32_t)v.y - k.lo, d2 = (uint32_t)v.z - k.lo, d3 = (uint32_t)v.w - k.lo;
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    if ((live & 1u) && d0 <= k.wm1) w[0] = semi_word<LDSSET>(k, d0 >> 5);
+    if ((live & 2u) && d1 <= k.wm1) w[1] = semi_word<LDSSET>(k, d1 >> 5);
+    if ((live & 4u) && d2 <= k.wm1) w[2] = semi_word<LDSSET>(k, d2 >> 5);
+    if ((live & 8u) && d3 <= k.wm1) w[3] = semi_word<LDSSET>(k, d3 >> 5);
+}
+
+__device__ __forceinline__ uint32_t semi_hits(const SemiArgs& k, int4 v, const uint32_t (&w)[4]) {
+    return ((w[0] >> (((uint32_t)v.x - k.lo) & 31u)) & 1u) | (((w[1] >> (((uint32_t)v.y - k.lo) & 31u)) & 1u) << 1) |
+           (((w[2] >> (((uint32_t)v.z - k.lo) & 31u)) & 1u) << 2) | (((w[3] >> (((uint32_t)v.w - k.lo) & 31u)) & 1u) << 3);
+}
+
+// live_tiles, then the key predicate on what is left.
+template <bool VEC, bool LDSSET, int U>
+__device__ __forceinline__ void semi_tiles(const WhereArgs& a, const SemiArgs& k, uint64_t row, int lane, uint32_t (&live)[U]) {
+    live_tiles<VEC, U>(a, row, lane, live);
+    int4 v[U];
+    uint32_t w[U][4];
+    const int32_t* __restrict__ p = k.key + row;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const u64 b = __ballot(live[u] != 0u);
+        v[u] = make_int4(0, 0, 0, 0);
+        if (b != 0 && line_live(b, lane)) v[u] = load4_nt<VEC>(p + (uint64_t)u * kTileRows);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) semi_words<LDSSET>(k, v[u], live[u], w[u]);
+#pragma unroll
+    for (int u = 0; u < U; u++) live[u] &= semi_hits(k, v[u], w[u]) ^ k.flip;
+}
+
+// The ragged tile, row by row.
+template <bool LDSSET>
+__device__ __forceinline__ uint32_t semi_ragged(const WhereArgs& a, const SemiArgs& k, uint64_t row, uint64_t end) {
+    uint32_t live = live_ragged(a, row, end);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        if (!(live & (1u << e))) continue;
+        const uint32_t d = (uint32_t)k.key[row + e] - k.lo;
+        const uint32_t hit = d <= k.wm1 ? (semi_word<LDSSET>(k, d >> 5) >> (d & 31u)) & 1u : 0u;
+        if (hit == (k.flip & 1u)) live &= ~(1u << e);
+    }
+    return live;
+}
+
+// k_where_mask's ballot words and counts, with the key predicate behind the ranges.
+template <bool VEC, bool LDSSET>
+__global__ __launch_bounds__(kTPB, 4) void k_semi_mask(WhereArgs a, SemiArgs k, uint64_t n, uint64_t rows_per_block,
+                                                       u64* __restrict__ bm, uint32_t* __restrict__ cnt) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+    semi_stage<LDSSET>(k);
+
+    auto put = [&](uint64_t t, uint32_t live) {
+        const u64 w0 = __ballot(live & 1u), w1 = __ballot(live & 2u), w2 = __ballot(live & 4u), w3 = __ballot(live & 8u);
+        const uint64_t wt = t / kWaveRows + (uint64_t)wave;
+        if (lane < 4) bm[wt * 4 + lane] = lane == 0 ? w0 : lane == 1 ? w1 : lane == 2 ? w2 : w3;
+        if (lane == 0) cnt[wt] = (uint32_t)(__popcll(w0) + __popcll(w1) + __popcll(w2) + __popcll(w3));
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)kWhU * kTileRows <= end; t += (uint64_t)kWhU * kTileRows) {
+        uint32_t live[kWhU];
+        semi_tiles<VEC, LDSSET, kWhU>(a, k, t + (uint64_t)tid * 4, lane, live);
+#pragma unroll
+        for (int u = 0; u < kWhU; u++) put(t + (uint64_t)u * kTileRows, live[u]);
+    }
+    for (; t + kTileRows <= end; t += kTileRows) {
+        uint32_t live[1];
+        semi_tiles<VEC, LDSSET, 1>(a, k, t + (uint64_t)tid * 4, lane, live);
+        put(t, live[0]);
+    }
+    if (t < end) put(t, semi_ragged<LDSSET>(a, k, t + (uint64_t)tid * 4, end));  // block-uniform
+}
+
+// k_where_agg with the key predicate behind the ranges; the value column comes last.
+template <bool VEC, bool LDSSET>
+__global__ __launch_bounds__(kTPB, 4) void k_semi_agg(WhereArgs a, SemiArgs k, const int32_t* __restrict__ val, uint64_t n,
+                                                      uint64_t rows_per_block, Partial* __restrict__ part) {
+    __shared__ Partial sp[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+    semi_stage<LDSSET>(k);
+
+    uint32_t cnt = 0;
+    long long sum = 0;
+    int mn = INT_MAX, mx = INT_MIN;
+    auto fold1 = [&](bool p, int v) {
+        cnt += (uint32_t)p;
+        sum += p ? (long long)v : 0ll;
+        mn = min(mn, p ? v : INT_MAX);
+        mx = max(mx, p ? v : INT_MIN);
+    };
+    auto fold = [&](int4 v, uint32_t live) {
+        fold1(live & 1u, v.x);
+        fold1(live & 2u, v.y);
+        fold1(live & 4u, v.z);
+        fold1(live & 8u, v.w);
+    };
+    auto tiles = [&](auto uc, uint64_t t) {
+        constexpr int U = decltype(uc)::value;
+        const uint64_t row = t + (uint64_t)tid * 4;
+        uint32_t live[U];
+        semi_tiles<VEC, LDSSET, U>(a, k, row, lane, live);
+        u64 b[U];
+        int4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            b[u] = __ballot(live[u] != 0u);
+            if (b[u] != 0 && line_live(b[u], lane)) v[u] = load4_nt<VEC>(val + row + (uint64_t)u * kTileRows);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (live[u] != 0u) fold(v[u], live[u]);
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)kWhU * kTileRows <= end; t += (uint64_t)kWhU * kTileRows)
+        tiles(std::integral_constant<int, kWhU>{}, t);
+    for (; t + kTileRows <= end; t += kTileRows) tiles(std::integral_constant<int, 1>{}, t);
+    if (t < end) {  // the column's ragged tile
+        const uint64_t row = t + (uint64_t)tid * 4;
+        const uint32_t live = semi_ragged<LDSSET>(a, k, row, end);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (live & (1u << e)) fold1(true, val[row + e]);
+    }
+
+    const u64 wc = wave_sum_u64((u64)cnt);
+    sum = wave_sum_i64(sum);
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    if (lane == 0) sp[wave] = Partial{wc, sum, mn, mx, 0ull};
+    __syncthreads();
+    if (tid == 0) {
+        Partial r = sp[0];
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) {
+            r.count += sp[w].count;
+            r.sum += sp[w].sum;
+            r.mn = min(r.mn, sp[w].mn);
+            r.mx = max(r.mx, sp[w].mx);
+        }
+        part[blockIdx.x] = r;
+    }
+}
+
 // The aggregate over no rows, in the stream's order.
 __global__ void k_where_empty(mq_agg* __restrict__ out) {
     if (threadIdx.x || blockIdx.x) return;
@@ -257,11 +446,14 @@ Layout layout(uint64_t n) {
 // What both entry points check and fold. `extra`: the payload (may be NULL) or the value
 // column (must not be). Returns MQ_OK with *empty set when some range matches no int32;
 // *vec: every column that is read lies on a 16-byte boundary.
-int prepare(const char* who, const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* extra,
-            bool extra_needed, uint64_t n, const void* d_ws, size_t ws_bytes, WhereArgs* a, bool* empty, bool* vec) {
-    if (ncols < 1 || ncols > MQ_WHERE_MAX_COLS) return set_err(MQ_EINVAL, "%s: ncols %d outside 1..%d", who, ncols, (int)MQ_WHERE_MAX_COLS);
+// min_cols: 1, or 0 where a key predicate stands behind the ranges (d_cols and h_ranges may then be NULL).
+int prepare(const char* who, int min_cols, const int32_t* const* d_cols, const mq_range* h_ranges, int ncols,
+            const int32_t* extra, bool extra_needed, uint64_t n, const void* d_ws, size_t ws_bytes, WhereArgs* a, bool* empty,
+            bool* vec) {
+    if (ncols < min_cols || ncols > MQ_WHERE_MAX_COLS)
+        return set_err(MQ_EINVAL, "%s: ncols %d outside %d..%d", who, ncols, min_cols, (int)MQ_WHERE_MAX_COLS);
     if (n >= (1ull << 31)) return set_err(MQ_EINVAL, "%s: n >= 2^31 (row ids are int32)", who);
-    if (!d_cols || !h_ranges) return set_err(MQ_EINVAL, "%s: NULL columns or ranges", who);
+    if (ncols && (!d_cols || !h_ranges)) return set_err(MQ_EINVAL, "%s: NULL columns or ranges", who);
     if (n) {
         for (int c = 0; c < ncols; c++)
             if (!d_cols[c] || (reinterpret_cast<uintptr_t>(d_cols[c]) & 3u))
@@ -272,6 +464,125 @@ int prepare(const char* who, const int32_t* const* d_cols, const mq_range* h_ran
     if (!d_ws || ws_bytes < layout(n).total || (reinterpret_cast<uintptr_t>(d_ws) & 15u))
         return set_err(MQ_EINVAL, "%s: workspace NULL, short or not 16-byte aligned", who);
     fold_ranges(d_cols, h_ranges, ncols, a, empty, vec);
+    return MQ_OK;
+}
+
+// Dynamic LDS beyond 64 KiB has to be asked for, per kernel.
+int allow_lds(const void* fn, size_t bytes) {
+    if (bytes <= 48u * 1024u) return MQ_OK;
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return MQ_OK;
+}
+
+// The positions of the rows that `a` (and the key predicate `k`, when given) leave: the mask
+// kernel, the scan and the expansion, on a checked workspace. lds: k's bitmap goes to LDS.
+int run_positions(DevState* s, const WhereArgs& a, bool vec, const SemiArgs* k, bool lds, const int32_t* d_payload, uint64_t n,
+                  int32_t* d_pos_out, uint64_t* d_count, void* d_ws, hipStream_t st) {
+    const Layout l = layout(n);
+    char* ws = static_cast<char*>(d_ws);
+    u64* bm = reinterpret_cast<u64*>(ws + l.bm);
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(ws + l.cnt);
+    u64* scratch = reinterpret_cast<u64*>(ws + l.scan);
+    uint32_t g;
+    uint64_t rpb;
+    int rc;
+    HIPCHK(hipMemsetAsync(cnt + l.nwt, 0, sizeof(uint32_t), st));  // the scan's last input (its output is K)
+    if (!k) {
+        geometry(s, n, vec ? reinterpret_cast<const void*>(&k_where_mask<true>) : reinterpret_cast<const void*>(&k_where_mask<false>),
+                 &g, &rpb, (uint64_t)kWhU * kTileRows);
+        if (vec)
+            hipLaunchKernelGGL((k_where_mask<true>), dim3(g), dim3(kTPB), 0, st, a, n, rpb, bm, cnt);
+        else
+            hipLaunchKernelGGL((k_where_mask<false>), dim3(g), dim3(kTPB), 0, st, a, n, rpb, bm, cnt);
+        LAUNCHCHK("k_where_mask");
+    } else {
+        const size_t dyn = lds ? (size_t)k->vec16 * 16 : 0;
+        const void* fn = vec ? (lds ? reinterpret_cast<const void*>(&k_semi_mask<true, true>) : reinterpret_cast<const void*>(&k_semi_mask<true, false>))
+                             : (lds ? reinterpret_cast<const void*>(&k_semi_mask<false, true>) : reinterpret_cast<const void*>(&k_semi_mask<false, false>));
+        if ((rc = allow_lds(fn, dyn))) return rc;
+        geometry(s, n, fn, &g, &rpb, (uint64_t)kWhU * kTileRows, dyn);
+        if (vec && lds)
+            hipLaunchKernelGGL((k_semi_mask<true, true>), dim3(g), dim3(kTPB), dyn, st, a, *k, n, rpb, bm, cnt);
+        else if (vec)
+            hipLaunchKernelGGL((k_semi_mask<true, false>), dim3(g), dim3(kTPB), 0, st, a, *k, n, rpb, bm, cnt);
+        else if (lds)
+            hipLaunchKernelGGL((k_semi_mask<false, true>), dim3(g), dim3(kTPB), dyn, st, a, *k, n, rpb, bm, cnt);
+        else
+            hipLaunchKernelGGL((k_semi_mask<false, false>), dim3(g), dim3(kTPB), 0, st, a, *k, n, rpb, bm, cnt);
+        LAUNCHCHK("k_semi_mask");
+    }
+    if ((rc = scan_u32_exclusive_u32(cnt, cnt, l.nwt + 1, scratch, st))) return rc;
+    const uint32_t blocks = (uint32_t)((l.nwt + kExpWt - 1) / kExpWt);
+    if (d_payload)
+        hipLaunchKernelGGL((k_where_expand<true>), dim3(blocks), dim3(kTPB), 0, st, bm, cnt, (uint32_t)l.nwt, n, d_payload,
+                           d_pos_out, reinterpret_cast<u64*>(d_count));
+    else
+        hipLaunchKernelGGL((k_where_expand<false>), dim3(blocks), dim3(kTPB), 0, st, bm, cnt, (uint32_t)l.nwt, n, d_payload,
+                           d_pos_out, reinterpret_cast<u64*>(d_count));
+    LAUNCHCHK("k_where_expand");
+    return MQ_OK;
+}
+
+// The aggregate of d_val over those rows. vec: the predicate columns' alignment.
+int run_agg(DevState* s, const WhereArgs& a, bool vec, const SemiArgs* k, bool lds, const int32_t* d_val, uint64_t n,
+            mq_agg* d_out, void* d_ws, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    vec = vec && aligned16(d_val);
+    uint32_t g;
+    uint64_t rpb;
+    Partial* part = static_cast<Partial*>(d_ws);
+    if (!k) {
+        geometry(s, n, vec ? reinterpret_cast<const void*>(&k_where_agg<true>) : reinterpret_cast<const void*>(&k_where_agg<false>),
+                 &g, &rpb, (uint64_t)kWhU * kTileRows);
+        if (vec)
+            hipLaunchKernelGGL((k_where_agg<true>), dim3(g), dim3(kTPB), 0, st, a, d_val, n, rpb, part);
+        else
+            hipLaunchKernelGGL((k_where_agg<false>), dim3(g), dim3(kTPB), 0, st, a, d_val, n, rpb, part);
+        LAUNCHCHK("k_where_agg");
+    } else {
+        const size_t dyn = lds ? (size_t)k->vec16 * 16 : 0;
+        const void* fn = vec ? (lds ? reinterpret_cast<const void*>(&k_semi_agg<true, true>) : reinterpret_cast<const void*>(&k_semi_agg<true, false>))
+                             : (lds ? reinterpret_cast<const void*>(&k_semi_agg<false, true>) : reinterpret_cast<const void*>(&k_semi_agg<false, false>));
+        int rc;
+        if ((rc = allow_lds(fn, dyn))) return rc;
+        geometry(s, n, fn, &g, &rpb, (uint64_t)kWhU * kTileRows, dyn);
+        if (vec && lds)
+            hipLaunchKernelGGL((k_semi_agg<true, true>), dim3(g), dim3(kTPB), dyn, st, a, *k, d_val, n, rpb, part);
+        else if (vec)
+            hipLaunchKernelGGL((k_semi_agg<true, false>), dim3(g), dim3(kTPB), 0, st, a, *k, d_val, n, rpb, part);
+        else if (lds)
+            hipLaunchKernelGGL((k_semi_agg<false, true>), dim3(g), dim3(kTPB), dyn, st, a, *k, d_val, n, rpb, part);
+        else
+            hipLaunchKernelGGL((k_semi_agg<false, false>), dim3(g), dim3(kTPB), 0, st, a, *k, d_val, n, rpb, part);
+        LAUNCHCHK("k_semi_agg");
+    }
+    return mq_combine_partials(d_ws, g, d_out, stream);
+}
+
+// AUTO copies the set into LDS up to kSemiLdsBytes; a forced LDS path takes what one block
+// can hold beside the aggregate's partials (kSemiLdsMax).
+// NOT YET MEASURED: 32 KiB keeps 5 blocks a CU resident (160 KiB of LDS); tools/bench_semi.py
+// sweeps 2^14..2^17 bytes through both forced paths to settle it.
+constexpr uint64_t kSemiLdsBytes = 32u * 1024u;
+constexpr uint64_t kSemiLdsMax = 128u * 1024u;
+
+// What mq_semi_positions and mq_semi_agg check and fold beyond prepare(). *lds: the path;
+// *trivial: the set is empty (no key predicate is left: anti keeps every row, semi none).
+int semi_prepare(const char* who, const int32_t* d_key, const mq_keyset* ks, int anti, int path, uint64_t n, bool* vec,
+                 SemiArgs* k, bool* lds, bool* trivial) {
+    if (!ks) return set_err(MQ_EINVAL, "%s: NULL key set", who);
+    if (path != MQ_SEMI_AUTO && path != MQ_SEMI_LDS && path != MQ_SEMI_GLOBAL) return set_err(MQ_EINVAL, "%s: path %d", who, path);
+    if (path == MQ_SEMI_LDS && ks->bytes > kSemiLdsMax)
+        return set_err(MQ_EINVAL, "%s: a set of %llu bytes does not fit in LDS (%llu)", who, (u64)ks->bytes, (u64)kSemiLdsMax);
+    if (n && (!d_key || (reinterpret_cast<uintptr_t>(d_key) & 3u))) return set_err(MQ_EINVAL, "%s: key column NULL or not 4-byte aligned", who);
+    int dev = -1;
+    int rc = current_device(&dev);
+    if (rc) return rc;
+    if (dev != ks->dev) return set_err(MQ_EINVAL, "%s: the key set lives on device %d, the call runs on %d", who, ks->dev, dev);
+    *trivial = ks->lo > ks->hi;
+    if (!*trivial) *vec = *vec && aligned16(d_key);  // an empty set: the key column is not read
+    *k = SemiArgs{d_key, ks->bits, (uint32_t)ks->lo, (uint32_t)ks->hi - (uint32_t)ks->lo, (uint32_t)(ks->bytes / 16), anti ? 15u : 0u};
+    *lds = path == MQ_SEMI_LDS || (path == MQ_SEMI_AUTO && ks->bytes <= kSemiLdsBytes);
     return MQ_OK;
 }
 
@@ -291,38 +602,14 @@ int mq_where_positions(const int32_t* const* d_cols, const mq_range* h_ranges, i
         return set_err(MQ_EINVAL, "mq_where_positions: output NULL or not 4-byte aligned");
     WhereArgs a;
     bool empty, vec;
-    if ((rc = prepare("mq_where_positions", d_cols, h_ranges, ncols, d_payload, false, n, d_ws, ws_bytes, &a, &empty, &vec)))
+    if ((rc = prepare("mq_where_positions", 1, d_cols, h_ranges, ncols, d_payload, false, n, d_ws, ws_bytes, &a, &empty, &vec)))
         return rc;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0 || empty) {
         HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
         return MQ_OK;
     }
-    const Layout l = layout(n);
-    char* ws = static_cast<char*>(d_ws);
-    u64* bm = reinterpret_cast<u64*>(ws + l.bm);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(ws + l.cnt);
-    u64* scratch = reinterpret_cast<u64*>(ws + l.scan);
-    uint32_t g;
-    uint64_t rpb;
-    geometry(s, n, vec ? reinterpret_cast<const void*>(&k_where_mask<true>) : reinterpret_cast<const void*>(&k_where_mask<false>),
-             &g, &rpb, (uint64_t)kWhU * kTileRows);
-    HIPCHK(hipMemsetAsync(cnt + l.nwt, 0, sizeof(uint32_t), st));  // the scan's last input (its output is K)
-    if (vec)
-        hipLaunchKernelGGL((k_where_mask<true>), dim3(g), dim3(kTPB), 0, st, a, n, rpb, bm, cnt);
-    else
-        hipLaunchKernelGGL((k_where_mask<false>), dim3(g), dim3(kTPB), 0, st, a, n, rpb, bm, cnt);
-    LAUNCHCHK("k_where_mask");
-    if ((rc = scan_u32_exclusive_u32(cnt, cnt, l.nwt + 1, scratch, st))) return rc;
-    const uint32_t blocks = (uint32_t)((l.nwt + kExpWt - 1) / kExpWt);
-    if (d_payload)
-        hipLaunchKernelGGL((k_where_expand<true>), dim3(blocks), dim3(kTPB), 0, st, bm, cnt, (uint32_t)l.nwt, n, d_payload,
-                           d_pos_out, reinterpret_cast<u64*>(d_count));
-    else
-        hipLaunchKernelGGL((k_where_expand<false>), dim3(blocks), dim3(kTPB), 0, st, bm, cnt, (uint32_t)l.nwt, n, d_payload,
-                           d_pos_out, reinterpret_cast<u64*>(d_count));
-    LAUNCHCHK("k_where_expand");
-    return MQ_OK;
+    return run_positions(s, a, vec, nullptr, false, d_payload, n, d_pos_out, d_count, d_ws, st);
 }
 
 int mq_where_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* d_val, uint64_t n,
@@ -333,25 +620,66 @@ int mq_where_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int nco
     if (!d_out) return set_err(MQ_EINVAL, "mq_where_agg: NULL output");
     WhereArgs a;
     bool empty, vec;
-    if ((rc = prepare("mq_where_agg", d_cols, h_ranges, ncols, d_val, true, n, d_ws, ws_bytes, &a, &empty, &vec))) return rc;
+    if ((rc = prepare("mq_where_agg", 1, d_cols, h_ranges, ncols, d_val, true, n, d_ws, ws_bytes, &a, &empty, &vec))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0 || empty) {
         hipLaunchKernelGGL(k_where_empty, dim3(1), dim3(64), 0, st, d_out);
         LAUNCHCHK("k_where_empty");
         return MQ_OK;
     }
-    vec = vec && aligned16(d_val);
-    uint32_t g;
-    uint64_t rpb;
-    geometry(s, n, vec ? reinterpret_cast<const void*>(&k_where_agg<true>) : reinterpret_cast<const void*>(&k_where_agg<false>),
-             &g, &rpb, (uint64_t)kWhU * kTileRows);
-    Partial* part = static_cast<Partial*>(d_ws);
-    if (vec)
-        hipLaunchKernelGGL((k_where_agg<true>), dim3(g), dim3(kTPB), 0, st, a, d_val, n, rpb, part);
-    else
-        hipLaunchKernelGGL((k_where_agg<false>), dim3(g), dim3(kTPB), 0, st, a, d_val, n, rpb, part);
-    LAUNCHCHK("k_where_agg");
-    return mq_combine_partials(d_ws, g, d_out, stream);
+    return run_agg(s, a, vec, nullptr, false, d_val, n, d_out, d_ws, stream);
+}
+
+size_t mq_semi_workspace_bytes(uint64_t n) { return layout(n).total; }
+
+int mq_semi_auto_path(uint64_t set_bytes) { return set_bytes <= kSemiLdsBytes ? MQ_SEMI_LDS : MQ_SEMI_GLOBAL; }
+
+int mq_semi_positions(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* d_key,
+                      const mq_keyset* ks, int anti, int path, const int32_t* d_payload, uint64_t n, int32_t* d_pos_out,
+                      uint64_t* d_count, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "mq_semi_positions";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (!d_count) return set_err(MQ_EINVAL, "%s: NULL count", who);
+    if (n && (!d_pos_out || (reinterpret_cast<uintptr_t>(d_pos_out) & 3u)))
+        return set_err(MQ_EINVAL, "%s: output NULL or not 4-byte aligned", who);
+    WhereArgs a;
+    SemiArgs k;
+    bool empty, vec, lds, trivial;
+    if ((rc = prepare(who, 0, d_cols, h_ranges, ncols, d_payload, false, n, d_ws, ws_bytes, &a, &empty, &vec))) return rc;
+    if ((rc = semi_prepare(who, d_key, ks, anti, path, n, &vec, &k, &lds, &trivial))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0 || empty || (trivial && !anti)) {
+        HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+        return MQ_OK;
+    }
+    // NOT IN the empty set: the ranges alone, as mq_where_positions runs them
+    if (trivial) return run_positions(s, a, vec, nullptr, false, d_payload, n, d_pos_out, d_count, d_ws, st);
+    return run_positions(s, a, vec, &k, lds, d_payload, n, d_pos_out, d_count, d_ws, st);
+}
+
+int mq_semi_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* d_key, const mq_keyset* ks,
+                int anti, int path, const int32_t* d_val, uint64_t n, mq_agg* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* who = "mq_semi_agg";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (!d_out) return set_err(MQ_EINVAL, "%s: NULL output", who);
+    WhereArgs a;
+    SemiArgs k;
+    bool empty, vec, lds, trivial;
+    if ((rc = prepare(who, 0, d_cols, h_ranges, ncols, d_val, true, n, d_ws, ws_bytes, &a, &empty, &vec))) return rc;
+    if ((rc = semi_prepare(who, d_key, ks, anti, path, n, &vec, &k, &lds, &trivial))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0 || empty || (trivial && !anti)) {
+        hipLaunchKernelGGL(k_where_empty, dim3(1), dim3(64), 0, st, d_out);
+        LAUNCHCHK("k_where_empty");
+        return MQ_OK;
+    }
+    // NOT IN the empty set: the ranges alone, as mq_where_agg runs them
+    if (trivial) return run_agg(s, a, vec, nullptr, false, d_val, n, d_out, d_ws, stream);
+    return run_agg(s, a, vec, &k, lds, d_val, n, d_out, d_ws, stream);
 }
 
 }  // extern "C"

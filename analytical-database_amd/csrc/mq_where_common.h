@@ -1,7 +1,8 @@
 // mq_where_common.h — internal (not exported) pieces shared by the kernels that stream
 // under a conjunction of range predicates (mq_where.hip, k_group_where_dense in
 // mq_group.hip): the folded predicates as kernel arguments, a lane's surviving rows per
-// tile with the dead 128-byte lines of the later columns skipped, and the host's fold.
+// tile with the dead 128-byte lines of the later columns skipped, and the host's fold; and the
+// key set that mq_keyset.hip builds and mq_where.hip's semi-join kernels probe.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -82,6 +83,16 @@ __device__ __forceinline__ uint32_t live_ragged(const WhereArgs& a, uint64_t row
     return live;
 }
 
+// The key set's lookup as kernel arguments (mq_where.hip's k_semi_*): key k is in the set
+// when d = (uint32)(k - lo) <= wm1 and bit d of `bits` is set.
+struct SemiArgs {
+    const int32_t* key;
+    const uint32_t* bits;
+    uint32_t lo, wm1;
+    uint32_t vec16;  // the bitmap in 16-byte pieces (what an LDS block copies)
+    uint32_t flip;   // 0: semi (key IN set); 15: anti (key NOT IN set), xor'ed onto the hit nibble
+};
+
 // The host's fold of ncols checked (column, range) pairs into *a. A range that matches
 // every int32 drops out (its column is not read). *empty: some range matches no int32 (*a
 // is then incomplete); *vec: every column that is read lies on a 16-byte boundary.
@@ -106,3 +117,13 @@ inline void fold_ranges(const int32_t* const* d_cols, const mq_range* h_ranges, 
 }
 
 }  // namespace mqi
+
+// A key set (mq_keyset_build in mq_keyset.hip, probed by mq_semi_* in mq_where.hip): one bit
+// per value of [lo, hi], immutable once built.
+struct mq_keyset {
+    int dev;
+    int32_t lo, hi;     // lo > hi: the empty set (bits == nullptr)
+    uint64_t distinct;
+    uint64_t bytes;     // of the bitmap: a multiple of 16, the padding zero
+    uint32_t* bits;     // pool_alloc'd
+};

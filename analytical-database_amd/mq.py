@@ -28,6 +28,7 @@ MQ_GROUP_MAX_KEYS = 4
 MQ_TOPK_AUTO, MQ_TOPK_SELECT, MQ_TOPK_SORT = 0, 1, 2
 MQ_TOPK_SORT_DIV = 4
 MQ_WHERE_MAX_COLS = 8
+MQ_SEMI_AUTO, MQ_SEMI_LDS, MQ_SEMI_GLOBAL = 0, 1, 2
 MQ_JOIN_STATE_WORDS = 3  # include/mq_device.h mq_join_state
 (MQ_JOIN_STATE_PART, MQ_JOIN_STATE_DUPW, MQ_JOIN_STATE_PACKED, MQ_JOIN_STATE_RS, MQ_JOIN_STATE_PRUNS,
  MQ_JOIN_STATE_RUN2, MQ_JOIN_STATE_DEFERRED, MQ_JOIN_STATE_ROW_WRITE) = (1 << b for b in range(8))
@@ -45,6 +46,10 @@ class MqTopkInfo(C.Structure):  # include/mq_device.h mq_topk_info
 
 class MqRange(C.Structure):  # include/mq_device.h mq_range
     _fields_ = [("has_low", C.c_int32), ("low", C.c_int32), ("has_high", C.c_int32), ("high", C.c_int32)]
+
+
+class MqKeysetInfo(C.Structure):  # include/mq_device.h mq_keyset_info
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("distinct", C.c_uint64), ("bytes", C.c_uint64)]
 
 
 class ColumnIndex(C.Structure):
@@ -214,6 +219,13 @@ _SIGS = {
     "mq_where_workspace_bytes": (_sz, [_u64]),
     "mq_where_positions": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "mq_where_agg": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "mq_keyset_build": (_int, [_vp, _u64, _int, _i32, _i32, C.POINTER(_vp), C.POINTER(MqKeysetInfo), _vp]),
+    "mq_keyset_free": (_int, [_vp]),
+    "mq_semi_workspace_bytes": (_sz, [_u64]),
+    "mq_semi_auto_path": (_int, [_u64]),
+    "mq_semi_positions": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _vp, _int, _int, _vp, _u64, _vp, _vp, _vp,
+                                 _sz, _vp]),
+    "mq_semi_agg": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _vp, _int, _int, _vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -262,6 +274,12 @@ _SIGS = {
                            C.POINTER(C.POINTER(_int)), _int, _PR, _PS]),
     "aggregate_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
                                          C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn), _PS]),
+    "select_where_in": (_PR, [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                              C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn),
+                              C.POINTER(GeneralizedColumn), C.c_bool, _PR, _PS]),
+    "aggregate_where_in": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                                            C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn),
+                                            C.POINTER(GeneralizedColumn), C.c_bool, C.POINTER(GeneralizedColumn), _PS]),
     "group_aggregate_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
                                                C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn),
                                                C.POINTER(GeneralizedColumn), _PS]),

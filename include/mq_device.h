@@ -648,6 +648,70 @@ int mq_where_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int nco
                  const int32_t* d_val, uint64_t n, mq_agg* d_out /* device */,
                  void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- WHERE ... AND k [NOT] IN (SELECT ...): semi and anti join in one pass ----
+ * A key set is the subquery's column as a bitmap: one bit per value of its span [lo, hi],
+ * bit (uint32)(key - lo) for `key`, in 32-bit words, rounded up to 16 bytes and zeroed (512 MiB
+ * at the full int32 span, so the span needs no second representation).
+ * build: has_bounds gives the span as {lo, hi}, inclusive (as mq_group_plan's key bounds): a key
+ *        outside it fails the build with MQ_EINVAL, everything released and *out = NULL.
+ *        Without bounds the span is the column's min and max, one more read of the keys
+ *        (mq_reduce). One streaming pass sets the bits (a global atomic OR, skipped when the
+ *        bit is seen set already: a column of one hot key does not queue n1 atomics on one
+ *        address), a second small kernel counts them: h_info->distinct is COUNT(DISTINCT) of the
+ *        column. The call SYNCHRONISES `stream` (the host reads the bounds and the count);
+ *        once it returns the handle is immutable and may be probed on any stream of its
+ *        device, any number of times, concurrently. n1 == 0 gives the empty set (lo = 0,
+ *        hi = -1, no bitmap) and a handle to free. mq_keyset_free: once every probe of the
+ *        handle has completed (the caller synchronises); NULL is fine.
+ *        MQ_EINVAL: n1 >= 2^31, d_keys NULL or not 4-byte aligned with n1 > 0, lo > hi with
+ *        has_bounds, a NULL out. MQ_ENOMEM when the bitmap cannot be allocated.
+ * probe: row i matches when every one of the ncols (0 .. MQ_WHERE_MAX_COLS) ranges holds, with
+ *        mq_where_positions' semantics exactly, and d_key[i] is in the set; with anti != 0,
+ *        when d_key[i] is NOT in the set. A key outside [lo, hi] is not in the set (one
+ *        unsigned compare, right at both ends of int32 and for the full span). Outputs,
+ *        ordering, payload, the empty aggregate and the workspace (mq_semi_workspace_bytes(n)
+ *        bytes, 16-byte aligned) are mq_where_positions' and mq_where_agg's; with ncols == 0
+ *        d_cols and h_ranges may be NULL. d_key may be a predicate column or the value column.
+ *        The ranges are evaluated first, in the order given; of the key column only the
+ *        128-byte lines that still hold a row are requested, the set is looked up for
+ *        surviving rows only, and the aggregate's value column follows under the same rule.
+ *        With ncols == 0 the key column is the one read whole.
+ * path:  MQ_SEMI_LDS: every block copies the bitmap into LDS first and looks up there;
+ *        MQ_SEMI_GLOBAL: the bit's word is a cached load (the bitmap stays in L2 and the
+ *        Infinity Cache; the columns pass by with non-temporal loads). MQ_SEMI_AUTO takes LDS
+ *        for a bitmap of up to mq_semi_auto_path's threshold. Forcing MQ_SEMI_LDS on a
+ *        bitmap above 128 KiB is MQ_EINVAL. The result does not depend on the path.
+ * Taken on the host, with no launch over the columns: the empty set gives K = 0 / the empty
+ * aggregate (anti == 0) or exactly mq_where_positions / mq_where_agg on the ranges (anti != 0;
+ * every row when ncols == 0); a range that no int32 satisfies gives K = 0 as before.
+ * Both probes are asynchronous on `stream`, which must belong to the key set's device.
+ * MQ_EINVAL, with nothing written: ncols outside 0..8, n >= 2^31, a NULL ks, a NULL or not
+ * 4-byte aligned column, key, value, payload or output with n > 0, a NULL count or aggregate,
+ * a NULL, short or misaligned workspace, a path that is none of the three, a key set of
+ * another device. Nothing here has been measured on a device yet: DESIGN.md §3.17. */
+typedef struct mq_keyset mq_keyset;
+typedef struct mq_keyset_info {
+    int32_t  lo, hi;      /* the set's span, inclusive (lo > hi: the empty set) */
+    uint64_t distinct;    /* number of different keys = COUNT(DISTINCT) of the column */
+    uint64_t bytes;       /* size of the bitmap */
+} mq_keyset_info;
+int mq_keyset_build(const int32_t* d_keys, uint64_t n1,
+                    int has_bounds, int32_t lo, int32_t hi,
+                    mq_keyset** out, mq_keyset_info* h_info /* may be NULL */, void* stream);
+int mq_keyset_free(mq_keyset* ks);
+enum { MQ_SEMI_AUTO = 0, MQ_SEMI_LDS = 1, MQ_SEMI_GLOBAL = 2 };
+size_t mq_semi_workspace_bytes(uint64_t n);             /* needs no device */
+int mq_semi_auto_path(uint64_t set_bytes);              /* needs no device: MQ_SEMI_LDS or MQ_SEMI_GLOBAL */
+int mq_semi_positions(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols /* 0..8 */,
+                      const int32_t* d_key, const mq_keyset* ks, int anti, int path,
+                      const int32_t* d_payload /* may be NULL */, uint64_t n,
+                      int32_t* d_pos_out /* capacity n */, uint64_t* d_count /* device */,
+                      void* d_ws, size_t ws_bytes, void* stream);
+int mq_semi_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols,
+                const int32_t* d_key, const mq_keyset* ks, int anti, int path,
+                const int32_t* d_val, uint64_t n, mq_agg* d_out /* device */,
+                void* d_ws, size_t ws_bytes, void* stream);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

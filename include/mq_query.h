@@ -326,6 +326,32 @@ Result* select_where(GeneralizedColumn** columns, int** lows, int** highs, int n
 Result** aggregate_where(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
                          GeneralizedColumn* values, Status* ret_status);
 
+/* ---- WHERE ... AND k [NOT] IN (SELECT ...) (not in the reference) ----
+ * select_where / aggregate_where with a semi join (anti: an anti join, NOT IN / NOT EXISTS)
+ * behind the ranges, in one pass (mq_keyset_build, mq_semi_positions and
+ * mq_semi_agg in mq_device.h): row i matches when every range holds and keys[i] is (anti: is
+ * not) among the values of `set_keys`. Today's spelling is hash_join's build, probe and
+ * per-row counts followed by a select over the counts; an anti join has none.
+ * `columns`, `lows`, `highs`, `positions` and `values` are select_where's and
+ * aggregate_where's; ncols is 0..8, and with ncols == 0 the first three may be NULL (the IN
+ * predicate alone). `keys` is a COLUMN or an INT RESULT as long as the columns; it may be one
+ * of them, or `values`. `set_keys` is a COLUMN or an INT RESULT of any length below 2^31, the
+ * subquery's output, for instance a select_where or fetch_column Result; duplicates are fine
+ * and an empty one is the empty set (semi: no row; anti: the ranges alone).
+ * The return values have select_where's and aggregate_where's shapes and ownership. The key
+ * set (one bit per value between the smallest and the largest set key, up to 512 MiB) is
+ * built per call and freed before returning. Resident copies and shadows of the inputs are
+ * used as the other operators use them. The operator runs on the calling device: a column
+ * held as row shards drops them and is split again on next use. ERROR and NULL (a "libmq:"
+ * line on stderr): no device, ncols outside 0..8, an argument of the wrong kind, different
+ * lengths, 2^31 rows or more, a device failure. */
+Result* select_where_in(GeneralizedColumn** columns, int** lows, int** highs, int ncols /* 0..8 */,
+                        GeneralizedColumn* keys, GeneralizedColumn* set_keys, bool anti,
+                        Result* positions /* NULL or INT, same length */, Status* ret_status);
+Result** aggregate_where_in(GeneralizedColumn** columns, int** lows, int** highs, int ncols,
+                            GeneralizedColumn* keys, GeneralizedColumn* set_keys, bool anti,
+                            GeneralizedColumn* values, Status* ret_status);
+
 /* ---- GROUP BY under a WHERE (not in the reference) ----
  * group_aggregate_where: SELECT key, count(*), sum(v), min(v), max(v) FROM t WHERE c0 IN [..)
  * AND c1 IN [..) ... GROUP BY key in one operator (mq_group_where_plan in
