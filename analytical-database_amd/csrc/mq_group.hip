@@ -80,6 +80,17 @@
 //   k_group_by_pack_pos: (P <= 2^32) code ^ 0x80000000 of the K matching rows, read from the
 //                        key columns through mq_where_positions' positions; the values are
 //                        gathered with mq_fetch and the sort path runs on the K codes.
+//
+// mq_group_join_plan is mq_group_where_plan with the group key found by a
+// key map (mq_keymap.hip: the dimension of an N:1 join as bitmap, rank directory and attributes
+// in key order), fact rows without a partner dropped, on the same handle. The attribute range
+// is the map's, so no bounds pass reads the fact table:
+//   k_group_join_dense : k_group_where_dense's stream with the lookup between the foreign key
+//                        column and the tables: the directory entry for surviving rows, the
+//                        attribute for hits, and of the value column only the lines that still
+//                        hold a joined row.
+//   sort path          : mq_semi_positions on the map's key set, the K joined rows' attributes
+//                        by mq_keymap_lookup and values by mq_fetch, then the sort path above.
 
 #include <hip/hip_runtime.h>
 
@@ -127,6 +138,7 @@ using u64 = unsigned long long;
 constexpr uint32_t kDenseSlots = 2048;
 constexpr int kGrpU = 4;                       // tiles of each column in flight per thread
 constexpr int kGwU = 4;                        // the same under predicates (k_group_where_dense)
+constexpr int kGjU = 4;                        // the same with a key map's lookup (k_group_join_dense)
 constexpr int kFoldSlots = 16;                 // slots per fold workgroup
 constexpr int kFoldParts = kTPB / kFoldSlots;  // block strides per slot
 constexpr int kSegBlocks = 2048;               // chunks of the sort path's passes
@@ -416,6 +428,170 @@ __global__ __launch_bounds__(kTPB, 4) void k_group_where_dense(WhereArgs a, cons
 #pragma unroll
         for (int e = 0; e < 4; e++)
             if (live & (1u << e)) update(keys[row + e], vals[row + e]);
+    }
+    if (run_open) flush();
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) out.bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * range;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        out.cnt[base + s] = s_cnt[s];
+        out.sum[base + s] = (long long)s_sum[s];
+        out.mn[base + s] = s_mn[s];
+        out.mx[base + s] = s_mx[s];
+    }
+}
+
+// k_group_where_dense with a key map's lookup (mq_where_common.h: MapArgs) between the key
+// column and the tables: of the foreign key column only the lines with a surviving row are
+// requested; for surviving rows only, the directory entry, then for hits the attribute;
+// live &= hit, the ballot is taken again, and of the value column only the lines that still
+// hold a joined row are requested. consume() then runs on the attributes. Within an iteration
+// all directory loads are issued, then all attribute loads, then all value loads, before the
+// first use. The fact columns pass by non-temporally; directory and attributes are plain cached
+// loads, so that they stay in L2 and the Infinity Cache. An attribute outside [lo, lo + range)
+// is counted, never used as an address.
+template <bool VEC>
+__global__ __launch_bounds__(kTPB, 4) void k_group_join_dense(WhereArgs a, MapArgs m, const int* vals, uint64_t n,
+                                                              uint64_t rows_per_block, int32_t lo, uint32_t range,
+                                                              DenseTabs out) {
+    __shared__ uint32_t s_cnt[kDenseSlots];
+    __shared__ u64 s_sum[kDenseSlots];
+    __shared__ int s_mn[kDenseSlots];
+    __shared__ int s_mx[kDenseSlots];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (uint32_t s = tid; s < range; s += kTPB) {
+        s_cnt[s] = 0u;
+        s_sum[s] = 0ull;
+        s_mn[s] = INT_MAX;
+        s_mx[s] = INT_MIN;
+    }
+    __syncthreads();
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    uint32_t nbad = 0;  // joined rows only
+    // the wave's run of tiles whose joined rows all share the attribute run_key, folded per lane
+    int run_key = 0;
+    bool run_open = false;  // wave-uniform
+    uint32_t r_cnt = 0;
+    long long r_sum = 0;
+    int r_mn = INT_MAX, r_mx = INT_MIN;
+
+    auto update = [&](int k, int v) {
+        const uint32_t s = (uint32_t)k - (uint32_t)lo;  // an attribute below lo wraps past range
+        if (s < range) {
+            atomicAdd(&s_cnt[s], 1u);
+            atomicAdd(&s_sum[s], (u64)(long long)v);
+            atomicMin(&s_mn[s], v);
+            atomicMax(&s_mx[s], v);
+        } else {
+            nbad++;
+        }
+    };
+    auto flush = [&]() {  // wave-uniform
+        const uint32_t c = (uint32_t)wave_sum_u64(r_cnt);  // <= the rows of the block's chunk < 2^31
+        const long long sm = wave_sum_i64(r_sum);
+        const int mn = wave_min(r_mn), mx = wave_max(r_mx);
+        if (lane == 0) {
+            const uint32_t s = (uint32_t)run_key - (uint32_t)lo;
+            if (s < range) {
+                atomicAdd(&s_cnt[s], c);
+                atomicAdd(&s_sum[s], (u64)sm);
+                atomicMin(&s_mn[s], mn);
+                atomicMax(&s_mx[s], mx);
+            } else {
+                nbad += c;
+            }
+        }
+        run_open = false;
+        r_cnt = 0;
+        r_sum = 0;
+        r_mn = INT_MAX;
+        r_mx = INT_MIN;
+    };
+    // k_group_where_dense's consume: k holds the attributes of the rows whose bit is set
+    auto consume = [&](int4 k, int4 v, uint32_t live, u64 b) {
+        const int kf = live & 1u ? k.x : live & 2u ? k.y : live & 4u ? k.z : k.w;  // the lane's first joined row
+        const int k0 = __builtin_amdgcn_readlane(kf, __builtin_ctzll(b));
+        const bool same = live == 0u || ((!(live & 1u) || k.x == k0) && (!(live & 2u) || k.y == k0) &&
+                                         (!(live & 4u) || k.z == k0) && (!(live & 8u) || k.w == k0));
+        if (__all(same)) {  // the joined rows of the wave's 256 share one attribute: into the run
+            if (run_open && k0 != run_key) flush();
+            run_key = k0;
+            run_open = true;
+            r_cnt += (uint32_t)__popc(live);
+            r_sum += (live & 1u ? (long long)v.x : 0ll) + (live & 2u ? (long long)v.y : 0ll) +
+                     (live & 4u ? (long long)v.z : 0ll) + (live & 8u ? (long long)v.w : 0ll);
+            r_mn = min(r_mn, min(min(live & 1u ? v.x : INT_MAX, live & 2u ? v.y : INT_MAX),
+                                 min(live & 4u ? v.z : INT_MAX, live & 8u ? v.w : INT_MAX)));
+            r_mx = max(r_mx, max(max(live & 1u ? v.x : INT_MIN, live & 2u ? v.y : INT_MIN),
+                                 max(live & 4u ? v.z : INT_MIN, live & 8u ? v.w : INT_MIN)));
+        } else {
+            if (live & 1u) update(k.x, v.x);
+            if (live & 2u) update(k.y, v.y);
+            if (live & 4u) update(k.z, v.z);
+            if (live & 8u) update(k.w, v.w);
+        }
+    };
+    auto tiles = [&](auto uc, uint64_t t) {
+        constexpr int U = decltype(uc)::value;
+        const uint64_t row = t + (uint64_t)tid * 4;
+        uint32_t live[U];
+        live_tiles<VEC, U>(a, row, lane, live);
+        u64 b[U];
+        int4 fk[U], at[U], v[U];
+        u64 e[U][4];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            b[u] = __ballot(live[u] != 0u);
+            fk[u] = make_int4(0, 0, 0, 0);
+            if (b[u] != 0 && line_live(b[u], lane)) fk[u] = load4_nt<VEC>(m.key + row + (uint64_t)u * kTileRows);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {  // the directory entries of the surviving rows
+            e[u][0] = live[u] & 1u ? map_entry(m, (uint32_t)fk[u].x - m.lo) : 0ull;
+            e[u][1] = live[u] & 2u ? map_entry(m, (uint32_t)fk[u].y - m.lo) : 0ull;
+            e[u][2] = live[u] & 4u ? map_entry(m, (uint32_t)fk[u].z - m.lo) : 0ull;
+            e[u][3] = live[u] & 8u ? map_entry(m, (uint32_t)fk[u].w - m.lo) : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {  // live &= hit; the attributes of the joined rows
+            const uint32_t d0 = (uint32_t)fk[u].x - m.lo, d1 = (uint32_t)fk[u].y - m.lo, d2 = (uint32_t)fk[u].z - m.lo,
+                           d3 = (uint32_t)fk[u].w - m.lo;
+            live[u] &= (uint32_t)map_hit(e[u][0], d0) | ((uint32_t)map_hit(e[u][1], d1) << 1) |
+                       ((uint32_t)map_hit(e[u][2], d2) << 2) | ((uint32_t)map_hit(e[u][3], d3) << 3);
+            at[u] = make_int4(0, 0, 0, 0);
+            if (live[u] & 1u) at[u].x = m.attr[map_rank(e[u][0], d0)];
+            if (live[u] & 2u) at[u].y = m.attr[map_rank(e[u][1], d1)];
+            if (live[u] & 4u) at[u].z = m.attr[map_rank(e[u][2], d2)];
+            if (live[u] & 8u) at[u].w = m.attr[map_rank(e[u][3], d3)];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            b[u] = __ballot(live[u] != 0u);
+            if (b[u] != 0 && line_live(b[u], lane)) v[u] = load4_nt<VEC>(vals + row + (uint64_t)u * kTileRows);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (b[u] != 0) consume(at[u], v[u], live[u], b[u]);  // wave-uniform
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)kGjU * kTileRows <= end; t += (uint64_t)kGjU * kTileRows)
+        tiles(std::integral_constant<int, kGjU>{}, t);
+    for (; t + kTileRows <= end; t += kTileRows) tiles(std::integral_constant<int, 1>{}, t);
+    if (t < end) {  // the column's ragged tile: row by row, none past the end
+        const uint64_t row = t + (uint64_t)tid * 4;
+        const uint32_t live = live_ragged(a, row, end);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (!(live & (1u << i))) continue;
+            const uint32_t d = (uint32_t)m.key[row + i] - m.lo;
+            const u64 en = map_entry(m, d);
+            if (map_hit(en, d)) update(m.attr[map_rank(en, d)], vals[row + i]);
+        }
     }
     if (run_open) flush();
     nbad = (uint32_t)wave_sum_u64(nbad);
@@ -1330,6 +1506,22 @@ int launch_where_dense(const DevState* s, const WhereArgs& a, const int32_t* key
     return MQ_OK;
 }
 
+template <bool VEC>
+int launch_join_dense(const DevState* s, const WhereArgs& a, const MapArgs& m, const int32_t* vals, uint64_t n, int32_t lo,
+                      uint32_t range, void** scratch_out, DenseTabs* tabs, uint32_t* blocks_out, hipStream_t st) {
+    uint32_t g;
+    uint64_t rpb;
+    geometry(s, n, reinterpret_cast<const void*>(&k_group_join_dense<VEC>), &g, &rpb, (uint64_t)kGjU * kTileRows);
+    void* scratch = pool_alloc(dense_scratch_bytes(g, range));
+    if (!scratch) return set_err(MQ_ENOMEM, "mq_group_join_plan: scratch allocation failed");
+    *tabs = dense_tabs(scratch, g, range);
+    *scratch_out = scratch;
+    *blocks_out = g;
+    hipLaunchKernelGGL((k_group_join_dense<VEC>), dim3(g), dim3(kTPB), 0, st, a, m, vals, n, rpb, lo, range, *tabs);
+    LAUNCHCHK("k_group_join_dense");
+    return MQ_OK;
+}
+
 template <int NK, bool VEC>
 int launch_by_dense(const DevState* s, const ByArgs& a, const int32_t* vals, uint64_t n, uint32_t range, void** scratch_out,
                     DenseTabs* tabs, uint32_t* blocks_out, hipStream_t st) {
@@ -1365,11 +1557,16 @@ int launch_by_where_dense(const DevState* s, const WhereArgs& w, const ByArgs& a
 // The dense path of the four plans; w: the folded predicates of mq_group_where_plan and
 // mq_group_by_where_plan (wvec: whether their columns are all 16-byte aligned), or NULL; rows:
 // NULL, or where the sum of the groups' counts goes; by: the nkeys key columns of
-// mq_group_by_plan and mq_group_by_where_plan (keys is not used then), or NULL.
+// mq_group_by_plan and mq_group_by_where_plan (keys is not used then), or NULL; jm: the key map
+// of mq_group_join_plan (with w; keys is its foreign key column), or NULL.
 int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_t* vals, uint64_t n, hipStream_t st,
                const WhereArgs* w = nullptr, bool wvec = false, uint64_t* rows = nullptr, const ByArgs* by = nullptr,
-               int nkeys = 0) {
-    const char* who = by && w ? "mq_group_by_where_plan" : by ? "mq_group_by_plan" : w ? "mq_group_where_plan" : "mq_group_plan";
+               int nkeys = 0, const MapArgs* jm = nullptr) {
+    const char* who = jm        ? "mq_group_join_plan"
+                      : by && w ? "mq_group_by_where_plan"
+                      : by      ? "mq_group_by_plan"
+                      : w       ? "mq_group_where_plan"
+                                : "mq_group_plan";
     g->tab = static_cast<char*>(pool_alloc(final_bytes(g->range)));
     if (!g->tab) return set_err(MQ_ENOMEM, "%s: table allocation failed", who);
     const FinalTab f = final_tab(g->tab, g->range);
@@ -1392,7 +1589,10 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
         rc = nkeys == 2   ? launch(std::integral_constant<int, 2>{})
              : nkeys == 3 ? launch(std::integral_constant<int, 3>{})
                           : launch(std::integral_constant<int, 4>{});
-    } else if (w)
+    } else if (jm)
+        rc = wvec && vk && vv ? launch_join_dense<true>(s, *w, *jm, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
+                              : launch_join_dense<false>(s, *w, *jm, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st);
+    else if (w)
         rc = wvec && vk && vv ? launch_where_dense<true>(s, *w, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st)
                               : launch_where_dense<false>(s, *w, keys, vals, n, g->lo, g->range, &scratch, &tabs, &blocks, st);
     else
@@ -1422,7 +1622,7 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
     pool_free(d_rows);
     if (rc) return rc;
     if (h[1] && by) return set_err(MQ_EINVAL, "%s: %llu rows with a key outside its column's bounds", who, h[1]);
-    if (h[1]) return set_err(MQ_EINVAL, "%s: %llu keys outside the bounds [%d, %lld]", who, h[1], g->lo,
+    if (h[1]) return set_err(MQ_EINVAL, "%s: %llu %s outside the bounds [%d, %lld]", who, h[1], jm ? "joined attributes" : "keys", g->lo,
                              (long long)g->lo + g->range - 1);
     g->groups = h[0];
     if (rows) *rows = r;
@@ -1804,6 +2004,114 @@ int mq_group_where_plan(const int32_t* const* d_cols, const mq_range* h_ranges, 
         }
         pool_free_on(ck, st);
         if (rc) return fail(rc);
+        rows = k;
+    }
+    if (h_path) *h_path = g->path;
+    if (h_rows) *h_rows = rows;
+    *h_groups = g->groups;
+    *out = g;
+    return MQ_OK;
+}
+
+int mq_group_join_plan(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* d_fkey,
+                       const mq_keymap* km, const int32_t* d_vals, uint64_t n, const int32_t* h_attr_bounds, int path,
+                       mq_group** out, uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream) {
+    const char* who = "mq_group_join_plan";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (out) *out = nullptr;
+    if (h_groups) *h_groups = 0;
+    if (h_rows) *h_rows = 0;
+    if (!out || !h_groups || !km || (ncols > 0 && (!d_cols || !h_ranges))) return set_err(MQ_EINVAL, "%s: NULL pointer", who);
+    if (ncols < 0 || ncols > MQ_WHERE_MAX_COLS)
+        return set_err(MQ_EINVAL, "%s: ncols %d outside 0..%d", who, ncols, (int)MQ_WHERE_MAX_COLS);
+    if (path != MQ_GROUP_AUTO && path != MQ_GROUP_DENSE && path != MQ_GROUP_SORT)
+        return set_err(MQ_EINVAL, "%s: path %d", who, path);
+    if (n >= (1ull << 31)) return set_err(MQ_EINVAL, "%s: n >= 2^31", who);
+    if (n) {
+        for (int c = 0; c < ncols; c++)
+            if (!d_cols[c] || (reinterpret_cast<uintptr_t>(d_cols[c]) & 3u))
+                return set_err(MQ_EINVAL, "%s: column %d NULL or not 4-byte aligned", who, c);
+        if (!d_fkey || !d_vals || (reinterpret_cast<uintptr_t>(d_fkey) & 3u) || (reinterpret_cast<uintptr_t>(d_vals) & 3u))
+            return set_err(MQ_EINVAL, "%s: key or value column NULL or not 4-byte aligned", who);
+        if (h_attr_bounds && h_attr_bounds[0] > h_attr_bounds[1])
+            return set_err(MQ_EINVAL, "%s: bounds [%d, %d] are empty", who, h_attr_bounds[0], h_attr_bounds[1]);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    if (dev != km->ks->dev) return set_err(MQ_EINVAL, "%s: the key map lives on device %d, the call runs on %d", who, km->ks->dev, dev);
+    WhereArgs a;
+    bool empty, vec;
+    fold_ranges(d_cols, h_ranges, ncols, &a, &empty, &vec);
+    mq_group* g = new (std::nothrow) mq_group();
+    if (!g) return set_err(MQ_ENOMEM, "%s: out of host memory", who);
+    g->dev = dev;
+    g->n = n;
+    g->vals = d_vals;
+    g->stream = st;
+    g->path = path == MQ_GROUP_SORT ? MQ_GROUP_SORT : MQ_GROUP_DENSE;  // what a plan without rows reports
+    auto no_groups = [&]() {
+        if (h_path) *h_path = g->path;
+        *out = g;
+        return MQ_OK;
+    };
+    if (n == 0 || empty || km->ks->lo > km->ks->hi) return no_groups();
+
+    // the attribute range of the small dimension is known since the build: no pass over the fact table
+    const int32_t lo = h_attr_bounds ? h_attr_bounds[0] : km->attr_lo, hi = h_attr_bounds ? h_attr_bounds[1] : km->attr_hi;
+    const int64_t range = (int64_t)hi - (int64_t)lo + 1;  // up to 2^32
+    if (path == MQ_GROUP_DENSE && range > (int64_t)kDenseSlots) {
+        delete g;
+        return set_err(MQ_EINVAL, "%s: attribute range %lld exceeds the dense path's %u slots", who, (long long)range, kDenseSlots);
+    }
+    g->path = path != MQ_GROUP_AUTO ? path : range <= (int64_t)kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
+    uint64_t rows = 0;
+    if (g->path == MQ_GROUP_DENSE) {
+        const MapArgs m = {d_fkey, km->dir, km->attr, (uint32_t)km->ks->lo, (uint32_t)km->ks->hi - (uint32_t)km->ks->lo};
+        g->lo = lo;
+        g->range = (uint32_t)range;
+        rc = plan_dense(s, g, d_fkey, d_vals, n, st, &a, vec, h_rows ? &rows : nullptr, nullptr, 0, &m);
+        if (rc) {
+            release(g, st);
+            return rc;
+        }
+    } else {
+        // the K joined rows' positions, their attributes and values, then the sort path on those
+        const size_t ws_bytes = mq_semi_workspace_bytes(n);
+        void* ws = pool_alloc(ws_bytes);
+        int32_t* pos = static_cast<int32_t*>(pool_alloc(n * 4));
+        u64* d_k = static_cast<u64*>(pool_alloc(sizeof(u64)));
+        u64 k = 0;
+        rc = ws && pos && d_k ? MQ_OK : set_err(MQ_ENOMEM, "%s: allocation failed", who);
+        if (!rc)
+            rc = mq_semi_positions(d_cols, h_ranges, ncols, d_fkey, km->ks, 0, MQ_SEMI_AUTO, nullptr, n, pos,
+                                   reinterpret_cast<uint64_t*>(d_k), ws, ws_bytes, stream);
+        if (!rc && hipMemcpyAsync(&k, d_k, sizeof k, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "%s: count download failed", who);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+        pool_free(d_k);
+        pool_free(ws);
+        int32_t* ck = nullptr;
+        if (!rc && k) {
+            ck = static_cast<int32_t*>(pool_alloc(k * 4));
+            g->own_vals = static_cast<int32_t*>(pool_alloc(k * 4));
+            if (!ck || !g->own_vals) rc = set_err(MQ_ENOMEM, "%s: allocation failed", who);
+            if (!rc) rc = mq_keymap_lookup(km, d_fkey, pos, k, 0, ck, nullptr, stream);  // every one is a hit
+            if (!rc) rc = mq_fetch(d_vals, pos, k, g->own_vals, stream);
+        }
+        pool_free_on(pos, st);  // the gathers queued above are its last readers
+        if (!rc && k) {
+            g->vals = g->own_vals;
+            g->n = k;
+            rc = plan_sort(g, ck, k, h_attr_bounds, st);  // synchronises
+        }
+        pool_free_on(ck, st);
+        if (rc) {
+            release(g, st);
+            return rc;
+        }
         rows = k;
     }
     if (h_path) *h_path = g->path;

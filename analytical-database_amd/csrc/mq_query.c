@@ -1447,6 +1447,49 @@ Result** group_aggregate_where(GeneralizedColumn** columns, int** lows, int** hi
     return group_results(who, g, groups, 1, rc, ret_status);
 }
 
+/* group_aggregate over the fact rows for which every range holds and whose foreign key has a
+ * partner in the dimension, grouped by the partner's attribute (no reference counterpart;
+ * DESIGN.md §3.18). The key map is built per call and freed before returning. */
+Result** group_aggregate_join(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn* fkeys,
+                              GeneralizedColumn* dim_keys, GeneralizedColumn* dim_attrs, GeneralizedColumn* values,
+                              Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "group_aggregate_join";
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t *dk = NULL, *dv = NULL, *ddk = NULL, *dda = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0, n1 = 0, n1a = 0;
+    const int a = dim_keys ? gcol_device(dim_keys, &ddk, &n1, ret_status) : -1;
+    if (a > 0) return NULL;
+    const int b = a < 0 ? a : dim_attrs ? gcol_device(dim_attrs, &dda, &n1a, ret_status) : -1;
+    if (b > 0) return NULL;
+    if (a < 0 || b < 0 || n1 != n1a || n1 >= ((size_t)1 << 31)) {
+        dml_fail(ret_status, who,
+                 a < 0 || b < 0 ? "dim_keys and dim_attrs must each be a Column or an INT Result"
+                 : n1 != n1a    ? "dim_keys and dim_attrs differ in length"
+                                : "2^31 dimension rows or more");
+        return NULL;
+    }
+    mq_keymap* km = NULL;
+    int rc = mq_keymap_build(ddk, dda, n1, 0, 0, 0, &km, NULL, g_stream); /* synchronises */
+    if (rc) {
+        fail(ret_status, who, rc);
+        return NULL;
+    }
+    Result** out = NULL;
+    if (in_keys(who, fkeys, &dk, &n, ret_status) ||
+        where_args_from(who, 0, 1, columns, lows, highs, ncols, values, d_cols, ranges, &dv, &n, ret_status))
+        goto done;
+    mq_group* g = NULL;
+    uint64_t groups = 0;
+    rc = mq_group_join_plan(d_cols, ranges, ncols, dk, km, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, NULL, g_stream);
+    out = group_results(who, g, groups, 1, rc, ret_status);
+done:
+    mq_stream_sync(g_stream);
+    mq_keymap_free(km);
+    return out;
+}
+
 /* The nkeys key columns of group_aggregate_by and group_aggregate_by_where on the calling
  * device: dk[0 .. nkeys). Every column is *n rows long, where the first one sets *n unless
  * have_n. 0; positive: a failure that has been reported; -1: an argument of the wrong kind;

@@ -1,8 +1,9 @@
 // mq_where_common.h — internal (not exported) pieces shared by the kernels that stream
 // under a conjunction of range predicates (mq_where.hip, k_group_where_dense in
 // mq_group.hip): the folded predicates as kernel arguments, a lane's surviving rows per
-// tile with the dead 128-byte lines of the later columns skipped, and the host's fold; and the
-// key set that mq_keyset.hip builds and mq_where.hip's semi-join kernels probe.
+// tile with the dead 128-byte lines of the later columns skipped, and the host's fold; the
+// key set that mq_keyset.hip builds and mq_where.hip's semi-join kernels probe; and the key
+// map that mq_keymap.hip builds on it and k_group_join_dense in mq_group.hip looks up.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -93,6 +94,25 @@ struct SemiArgs {
     uint32_t flip;   // 0: semi (key IN set); 15: anti (key NOT IN set), xor'ed onto the hit nibble
 };
 
+// The key map's lookup as kernel arguments (mq_keymap.hip, k_group_join_dense): key k has a
+// partner when d = (uint32)(k - lo) <= wm1 and bit d & 31 of the low half of e = dir[d >> 5] is
+// set; its attribute is attr[(e >> 32) + popc(low(e) & ((1 << (d & 31)) - 1))].
+struct MapArgs {
+    const int32_t* key;
+    const unsigned long long* dir;
+    const int32_t* attr;
+    uint32_t lo, wm1;
+};
+
+// The directory entry of offset d, or 0 (no bit set) for a key outside the span.
+__device__ __forceinline__ unsigned long long map_entry(const MapArgs& m, uint32_t d) {
+    return d <= m.wm1 ? m.dir[d >> 5] : 0ull;
+}
+__device__ __forceinline__ bool map_hit(unsigned long long e, uint32_t d) { return ((uint32_t)e >> (d & 31u)) & 1u; }
+__device__ __forceinline__ uint32_t map_rank(unsigned long long e, uint32_t d) {
+    return (uint32_t)(e >> 32) + (uint32_t)__popc((uint32_t)e & ((1u << (d & 31u)) - 1u));
+}
+
 // The host's fold of ncols checked (column, range) pairs into *a. A range that matches
 // every int32 drops out (its column is not read). *empty: some range matches no int32 (*a
 // is then incomplete); *vec: every column that is read lies on a 16-byte boundary.
@@ -126,4 +146,16 @@ struct mq_keyset {
     uint64_t distinct;
     uint64_t bytes;     // of the bitmap: a multiple of 16, the padding zero
     uint32_t* bits;     // pool_alloc'd
+};
+
+// A key map (mq_keymap_build in mq_keymap.hip): a key set over the dimension's primary key,
+// its rank directory and the attributes in key order; immutable once built.
+struct mq_keymap {
+    mq_keyset* ks;            // owned; lo > hi: the empty map (dir == attr == nullptr)
+    unsigned long long* dir;  // one entry per 32 keys of the span (per bitmap word, padding included):
+                              // low half the bitmap word, high half the set bits of all earlier words
+    int32_t* attr;            // attr_by_rank[n1]
+    int32_t attr_lo, attr_hi;
+    uint64_t n1;
+    uint64_t bytes;           // bitmap + directory + attributes
 };

@@ -52,6 +52,11 @@ class MqKeysetInfo(C.Structure):  # include/mq_device.h mq_keyset_info
     _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("distinct", C.c_uint64), ("bytes", C.c_uint64)]
 
 
+class MqKeymapInfo(C.Structure):  # include/mq_device.h mq_keymap_info
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("attr_lo", C.c_int32), ("attr_hi", C.c_int32),
+                ("entries", C.c_uint64), ("bytes", C.c_uint64)]
+
+
 class ColumnIndex(C.Structure):
     _fields_ = [("values", C.POINTER(C.c_int)), ("positions", C.POINTER(C.c_size_t))]
 
@@ -226,6 +231,14 @@ _SIGS = {
     "mq_semi_positions": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _vp, _int, _int, _vp, _u64, _vp, _vp, _vp,
                                  _sz, _vp]),
     "mq_semi_agg": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _vp, _int, _int, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "mq_keymap_bytes": (_sz, [_u64, _u64]),
+    "mq_keymap_geometry": (None, [_u64, C.POINTER(C.c_uint32), C.POINTER(_u64)]),
+    "mq_keymap_build": (_int, [_vp, _vp, _u64, _int, _i32, _i32, C.POINTER(_vp), C.POINTER(MqKeymapInfo), _vp]),
+    "mq_keymap_keyset": (_vp, [_vp]),
+    "mq_keymap_lookup": (_int, [_vp, _vp, _vp, _u64, _i32, _vp, _vp, _vp]),
+    "mq_keymap_free": (_int, [_vp]),
+    "mq_group_join_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _vp, _vp, _u64, _vp, _int, C.POINTER(_vp),
+                                  C.POINTER(_u64), C.POINTER(_int), C.POINTER(_u64), _vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -283,6 +296,10 @@ _SIGS = {
     "group_aggregate_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
                                                C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn),
                                                C.POINTER(GeneralizedColumn), _PS]),
+    "group_aggregate_join": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                                              C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn),
+                                              C.POINTER(GeneralizedColumn), C.POINTER(GeneralizedColumn),
+                                              C.POINTER(GeneralizedColumn), _PS]),
     "group_aggregate_by": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), _int, C.POINTER(GeneralizedColumn),
                                             _PS]),
     "group_aggregate_by_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),

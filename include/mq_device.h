@@ -712,6 +712,80 @@ int mq_semi_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int ncol
                 const int32_t* d_val, uint64_t n, mq_agg* d_out /* device */,
                 void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- GROUP BY an attribute of a joined dimension, in one pass ----
+ *   SELECT d.attr, count(*), sum(f.v), min(f.v), max(f.v) FROM f JOIN d ON f.fkey = d.key
+ *   WHERE f.c0 IN [..) AND ... GROUP BY d.attr
+ * A key map is the dimension (d_keys a primary key, d_attrs its attribute) as a map from key to
+ * attribute, in one representation for every span: the key set's bitmap over [lo, hi] (built by
+ * mq_keyset_build's code; mq_keymap_keyset returns it as an ordinary key set that the map
+ * owns), a rank directory of one uint64_t per 32 keys of the span (low 32 bits the bitmap word,
+ * high 32 bits the set bits of all earlier words, an exclusive prefix below 2^31) and the
+ * attributes in key order. A lookup is d = (uint32_t)(key - lo) <= hi - lo, one 8-byte load
+ * e = dir[d >> 5], a bit test, rank = (e >> 32) + popc((uint32_t)e & ((1u << (d & 31)) - 1)) and
+ * one 4-byte load attr_by_rank[rank]. At the full int32 span that is 512 MiB of bitmap plus
+ * 1 GiB of directory plus 4 * n1 bytes (mq_keymap_bytes(span, n1), span = hi - lo + 1 up to 2^32).
+ * build: the bounds are mq_keyset_build's (given, or one mq_reduce over the keys; a key outside
+ *        given bounds is MQ_EINVAL). The keys must be distinct: otherwise MQ_EINVAL,
+ *        mq_last_error() names the number of repeated keys, and everything is released. A
+ *        prefix pass over the bitmap words' popcounts writes the directory (a fixed grid of
+ *        chunks, mq_keymap_geometry: blocks and bitmap words a chunk, no device needed),
+ *        k_keymap_place stores every attribute at its key's rank, and one mq_reduce over the
+ *        attributes gives attr_lo / attr_hi. SYNCHRONISES `stream`; afterwards the handle is
+ *        immutable and may be probed on any stream of its device. n1 == 0 gives the empty map
+ *        (lo = 0, hi = -1, attr_lo = INT32_MAX, attr_hi = INT32_MIN) and a handle to free.
+ *        MQ_EINVAL otherwise as mq_keyset_build, and for NULL or misaligned attributes.
+ * lookup: the materialised N:1 join, SELECT d.attr FROM f JOIN d: for i < k < 2^31, with
+ *        key = d_keys[d_pos ? d_pos[i] : i], d_attr_out[i] = the key's attribute, or `missing`
+ *        when the key is not in the map; d_hit_out[i] (may be NULL) = 1 or 0. Grid-stride,
+ *        asynchronous on `stream`; nothing is written at or past entry k.
+ * mq_group_join_plan: with m[i] = every range holds for row i (mq_where_positions' meaning;
+ *        ncols == 0: every row, d_cols and h_ranges may then be NULL) and d_fkey[i] is in the
+ *        map, the result is exactly mq_group_plan over (attr(d_fkey[m]), d_vals[m]): an inner
+ *        join, fact rows without a partner are dropped. *h_rows (may be NULL) = the joined
+ *        rows. The handle is an ordinary mq_group with one key: mq_group_write (d_keys_out
+ *        receives the attributes) and mq_group_free serve it. Integer operations only: bitwise
+ *        the same whatever the path, the grid, the order of the predicates or the alignment.
+ *        h_attr_bounds (NULL or a host {lo, hi}, inclusive) constrains the attributes of JOINED
+ *        rows only; one outside them is MQ_EINVAL with everything released and is never used
+ *        as an address. NULL takes the map's attr_lo / attr_hi and costs no pass over the fact
+ *        table. The range picks the path as in mq_group_plan; MQ_GROUP_DENSE forced on a wider
+ *        range is MQ_EINVAL.
+ * dense: one streaming pass, k_group_join_dense: k_group_where_dense with the lookup between
+ *        the key column and the tables. Of d_fkey only the 128-byte lines with a surviving row
+ *        are requested; for surviving rows only, the directory entry and then, for hits, the
+ *        attribute; of d_vals only the lines that still hold a joined row. The fact columns
+ *        pass by with non-temporal loads, directory and attributes with plain cached loads.
+ * sort:  mq_semi_positions on the map's key set gives the K joined rows, mq_keymap_lookup
+ *        through them their attributes, mq_fetch their values (a buffer the handle owns), then
+ *        mq_group_plan's sort path on those.
+ * Settled on the host with no launch over the columns: n == 0, a range that no int32 satisfies,
+ * the empty map: zero groups and a handle to free. Pointer, ncols (0..8 here), n and path checks
+ * are mq_group_where_plan's; a key map of another device is MQ_EINVAL. Synchronises.
+ * Not measured on a device yet (tools/bench_group_join.py is the sweep). */
+typedef struct mq_keymap mq_keymap;
+typedef struct mq_keymap_info {
+    int32_t  lo, hi;            /* span of the keys, inclusive (lo > hi: empty map) */
+    int32_t  attr_lo, attr_hi;  /* min / max of the attributes (INT32_MAX / INT32_MIN when empty) */
+    uint64_t entries;           /* n1 */
+    uint64_t bytes;             /* device bytes held: bitmap + directory + attributes */
+} mq_keymap_info;
+size_t mq_keymap_bytes(uint64_t span, uint64_t n1);      /* needs no device */
+/* the directory's prefix pass over a span of `span` keys: blocks launched and bitmap words
+ * (32 keys each) in a block's chunk; needs no device, either pointer may be NULL */
+void mq_keymap_geometry(uint64_t span, uint32_t* prefix_blocks, uint64_t* prefix_chunk_words);
+int mq_keymap_build(const int32_t* d_keys, const int32_t* d_attrs, uint64_t n1,
+                    int has_bounds, int32_t lo, int32_t hi,
+                    mq_keymap** out, mq_keymap_info* h_info /* may be NULL */, void* stream);
+const mq_keyset* mq_keymap_keyset(const mq_keymap* km);  /* the same keys as a §3.17 key set; owned by km */
+int mq_keymap_lookup(const mq_keymap* km, const int32_t* d_keys, const int32_t* d_pos /* may be NULL */,
+                     uint64_t k, int32_t missing, int32_t* d_attr_out,
+                     uint8_t* d_hit_out /* may be NULL */, void* stream);
+int mq_keymap_free(mq_keymap* km);
+int mq_group_join_plan(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols /* 0..8 */,
+                       const int32_t* d_fkey, const mq_keymap* km, const int32_t* d_vals, uint64_t n,
+                       const int32_t* h_attr_bounds /* NULL: the map's attr_lo, attr_hi */, int path,
+                       mq_group** out, uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

@@ -413,6 +413,30 @@ Result** group_aggregate_by_where(GeneralizedColumn** columns, int** lows, int**
                                   GeneralizedColumn** keys, int nkeys, GeneralizedColumn* values,
                                   Status* ret_status);
 
+/* ---- GROUP BY an attribute of a joined dimension (not in the reference) ----
+ * group_aggregate_join: SELECT d.attr, count(*), sum(f.v), min(f.v), max(f.v) FROM f JOIN d ON
+ * f.fkey = d.key WHERE f.c0 IN [..) AND ... GROUP BY d.attr in one operator (DESIGN.md §3.18;
+ * mq_keymap_build and mq_group_join_plan in mq_device.h): what hash_join -> fetch_column x 2 ->
+ * group_aggregate returns behind a select_where, without the pair list, the gathered columns
+ * and the host round trips between them. `columns`, `lows`, `highs` and `ncols` are
+ * select_where_in's: ncols is 0..8, and with ncols == 0 the first three may be NULL. `fkeys`
+ * (the fact table's foreign key) and `values` are a COLUMN or an INT RESULT as long as the
+ * columns; `dim_keys` and `dim_attrs` are a COLUMN or an INT RESULT, equally long (below 2^31),
+ * and dim_keys holds every key once (a primary key). A fact row whose key has no partner is
+ * dropped (an inner join); an empty dimension gives five empty Results and OK. Returns
+ * group_aggregate's five Results under its ownership and shadow rules, one tuple per attribute
+ * with a joined row, ascending: [0] attributes (INT), [1] counts (LONG), [2] sums (LONG),
+ * [3] minima (INT), [4] maxima (INT). The key map (bitmap, rank directory and attributes over
+ * the span of dim_keys, up to 1.5 GiB + 4 bytes a key) is built per call and freed before
+ * returning. No attribute bounds are passed and none are searched for: the map knows its
+ * attributes' range. Runs on the calling device; a column held as row shards drops them and is
+ * split again on next use. ERROR and NULL (a "libmq:" line on stderr): no device, ncols outside
+ * 0..8, an argument of the wrong kind, different lengths, 2^31 rows or more, a key that occurs
+ * twice in dim_keys, a device failure. Not measured on a device yet. */
+Result** group_aggregate_join(GeneralizedColumn** columns, int** lows, int** highs, int ncols /* 0..8 */,
+                              GeneralizedColumn* fkeys, GeneralizedColumn* dim_keys,
+                              GeneralizedColumn* dim_attrs, GeneralizedColumn* values, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
