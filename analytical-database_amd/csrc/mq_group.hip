@@ -91,6 +91,18 @@
 //                        hold a joined row.
 //   sort path          : mq_semi_positions on the map's key set, the K joined rows' attributes
 //                        by mq_keymap_lookup and values by mq_fetch, then the sort path above.
+//
+// mq_group_star_plan is mq_group_by_where_plan over the rows that every term
+// of a star query keeps (mq_where_common.h: StarArgs; a fact column grouped through a key map,
+// filtered by a key set, or a group key itself), the tuple made of the maps' attributes and the
+// plain columns, on the same handle:
+//   k_group_star_dense : (P <= kDenseSlots) k_group_by_where_dense's stream and tables; term by
+//                        term the surviving lines of the term's column, the bitmap word or the
+//                        directory entry and attribute for surviving rows, the component added
+//                        to the row's code and checked against its own bounds.
+//   sort path          : mq_star_positions (mq_where.hip) gives the K joined rows,
+//                        k_group_star_pack_pos their codes read through the positions, mq_fetch
+//                        their values, then the sort path above on the codes.
 
 #include <hip/hip_runtime.h>
 
@@ -1306,6 +1318,308 @@ __global__ __launch_bounds__(kTPB) void k_group_by_pack_pos(ByArgs a, const int3
     if (lane == 0) bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
 }
 
+// ---- several joined dimensions and fact-side keys in one tuple (mq_group_star_plan) ----
+
+// Tiles of each column in flight per thread: kGjU with one term, by_tiles with more. NOT SWEPT:
+// taken over from the kernels this one is made of; the resource report only
+// shows that they fit 4 waves a SIMD without scratch.
+constexpr int star_tiles_in_flight(int nt) { return nt == 1 ? kGjU : by_tiles(nt); }
+
+// k_group_by_where_dense with the terms of a star query (mq_where_common.h: StarArgs) between
+// the predicates and the tables. Term by term, in the order given: the tiles are balloted again
+// and only the 128-byte lines of the term's column that still hold a row are requested
+// (non-temporal); a key set term loads the bitmap word for live rows and live &= hit; a key map
+// term loads the directory entry for live rows, live &= hit, then the attribute for hits (plain
+// cached loads, so that they stay in L2 and the Infinity Cache); a plain term's value is the
+// component. A component adds (comp - lo) * stride to the row's code and clears the row's
+// in-bounds bit when comp - lo > rm1 (row_code's rule: every component by itself). Within one
+// term all column loads of the iteration are issued, then all directory or bitmap loads, then
+// all attribute loads, before the first use. After the last term the value column's surviving
+// lines are loaded and consume() runs on slot = code, or kNoSlot for a row out of bounds, which
+// is counted and never used as an address. The kind of a term is uniform over the grid.
+template <int NT, bool VEC>
+__global__ __launch_bounds__(kTPB, 4) void k_group_star_dense(WhereArgs w, StarArgs s, const int* vals, uint64_t n,
+                                                              uint64_t rows_per_block, uint32_t range, DenseTabs out) {
+    constexpr int U = star_tiles_in_flight(NT);
+    __shared__ uint32_t s_cnt[kDenseSlots];
+    __shared__ u64 s_sum[kDenseSlots];
+    __shared__ int s_mn[kDenseSlots];
+    __shared__ int s_mx[kDenseSlots];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (uint32_t q = tid; q < range; q += kTPB) {
+        s_cnt[q] = 0u;
+        s_sum[q] = 0ull;
+        s_mn[q] = INT_MAX;
+        s_mx[q] = INT_MIN;
+    }
+    __syncthreads();
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    uint32_t nbad = 0;  // joined rows only
+    // the wave's run of tiles whose joined rows all share run_slot, folded per lane
+    uint32_t run_slot = 0;
+    bool run_open = false;  // wave-uniform
+    uint32_t r_cnt = 0;
+    long long r_sum = 0;
+    int r_mn = INT_MAX, r_mx = INT_MIN;
+
+    auto update = [&](uint32_t sl, int v) {
+        if (sl < range) {  // kNoSlot never is
+            atomicAdd(&s_cnt[sl], 1u);
+            atomicAdd(&s_sum[sl], (u64)(long long)v);
+            atomicMin(&s_mn[sl], v);
+            atomicMax(&s_mx[sl], v);
+        } else {
+            nbad++;
+        }
+    };
+    auto flush = [&]() {  // wave-uniform
+        const uint32_t c = (uint32_t)wave_sum_u64(r_cnt);  // <= the rows of the block's chunk < 2^31
+        const long long sm = wave_sum_i64(r_sum);
+        const int mn = wave_min(r_mn), mx = wave_max(r_mx);
+        if (lane == 0) {
+            if (run_slot < range) {
+                atomicAdd(&s_cnt[run_slot], c);
+                atomicAdd(&s_sum[run_slot], (u64)sm);
+                atomicMin(&s_mn[run_slot], mn);
+                atomicMax(&s_mx[run_slot], mx);
+            } else {
+                nbad += c;
+            }
+        }
+        run_open = false;
+        r_cnt = 0;
+        r_sum = 0;
+        r_mn = INT_MAX;
+        r_mx = INT_MIN;
+    };
+    // k_group_by_where_dense's consume on the slots of a full tile with a joined row in the wave
+    auto consume = [&](uint4 sl, int4 v, uint32_t live, u64 b) {
+        const uint32_t sf = live & 1u ? sl.x : live & 2u ? sl.y : live & 4u ? sl.z : sl.w;  // the lane's first joined slot
+        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane((int)sf, __builtin_ctzll(b));
+        const bool same = live == 0u || ((!(live & 1u) || sl.x == s0) && (!(live & 2u) || sl.y == s0) &&
+                                         (!(live & 4u) || sl.z == s0) && (!(live & 8u) || sl.w == s0));
+        if (__all(same)) {  // the joined rows of the wave's 256 share one slot: into the run
+            if (run_open && s0 != run_slot) flush();
+            run_slot = s0;
+            run_open = true;
+            r_cnt += (uint32_t)__popc(live);
+            r_sum += (live & 1u ? (long long)v.x : 0ll) + (live & 2u ? (long long)v.y : 0ll) +
+                     (live & 4u ? (long long)v.z : 0ll) + (live & 8u ? (long long)v.w : 0ll);
+            r_mn = min(r_mn, min(min(live & 1u ? v.x : INT_MAX, live & 2u ? v.y : INT_MAX),
+                                 min(live & 4u ? v.z : INT_MAX, live & 8u ? v.w : INT_MAX)));
+            r_mx = max(r_mx, max(max(live & 1u ? v.x : INT_MIN, live & 2u ? v.y : INT_MIN),
+                                 max(live & 4u ? v.z : INT_MIN, live & 8u ? v.w : INT_MIN)));
+        } else {
+            if (live & 1u) update(sl.x, v.x);
+            if (live & 2u) update(sl.y, v.y);
+            if (live & 4u) update(sl.z, v.z);
+            if (live & 8u) update(sl.w, v.w);
+        }
+    };
+    // One component of the lane's four rows into their codes and in-bounds bits.
+    auto add_comp = [&](const StarTerm& tm, int4 c, uint4& code, uint32_t& in) {
+        const uint32_t d0 = (uint32_t)c.x - tm.lo, d1 = (uint32_t)c.y - tm.lo, d2 = (uint32_t)c.z - tm.lo, d3 = (uint32_t)c.w - tm.lo;
+        in &= (uint32_t)(d0 <= tm.rm1) | ((uint32_t)(d1 <= tm.rm1) << 1) | ((uint32_t)(d2 <= tm.rm1) << 2) |
+              ((uint32_t)(d3 <= tm.rm1) << 3);
+        code.x += d0 * tm.stride;
+        code.y += d1 * tm.stride;
+        code.z += d2 * tm.stride;
+        code.w += d3 * tm.stride;
+    };
+    auto tiles = [&](auto tc, uint64_t t) {
+        constexpr int T = decltype(tc)::value;
+        const uint64_t row = t + (uint64_t)tid * 4;
+        uint32_t live[T], in[T];
+        uint4 code[T];
+        live_tiles<VEC, T>(w, row, lane, live);
+#pragma unroll
+        for (int u = 0; u < T; u++) {
+            in[u] = 15u;
+            code[u] = make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const StarTerm& tm = s.t[j];
+            int4 fk[T];
+#pragma unroll
+            for (int u = 0; u < T; u++) {
+                const u64 b = __ballot(live[u] != 0u);
+                fk[u] = make_int4(0, 0, 0, 0);
+                if (b != 0 && line_live(b, lane)) fk[u] = load4_nt<VEC>(tm.col + row + (uint64_t)u * kTileRows);
+            }
+            if (tm.kind == kStarSet) {  // grid-uniform
+                uint32_t bw[T][4];
+#pragma unroll
+                for (int u = 0; u < T; u++) {
+                    bw[u][0] = live[u] & 1u ? star_word(tm, (uint32_t)fk[u].x - tm.klo) : 0u;
+                    bw[u][1] = live[u] & 2u ? star_word(tm, (uint32_t)fk[u].y - tm.klo) : 0u;
+                    bw[u][2] = live[u] & 4u ? star_word(tm, (uint32_t)fk[u].z - tm.klo) : 0u;
+                    bw[u][3] = live[u] & 8u ? star_word(tm, (uint32_t)fk[u].w - tm.klo) : 0u;
+                }
+#pragma unroll
+                for (int u = 0; u < T; u++)
+                    live[u] &= ((bw[u][0] >> (((uint32_t)fk[u].x - tm.klo) & 31u)) & 1u) |
+                               (((bw[u][1] >> (((uint32_t)fk[u].y - tm.klo) & 31u)) & 1u) << 1) |
+                               (((bw[u][2] >> (((uint32_t)fk[u].z - tm.klo) & 31u)) & 1u) << 2) |
+                               (((bw[u][3] >> (((uint32_t)fk[u].w - tm.klo) & 31u)) & 1u) << 3);
+            } else if (tm.kind == kStarMap) {
+                const MapArgs m = star_map(tm);
+                u64 e[T][4];
+                int4 at[T];
+#pragma unroll
+                for (int u = 0; u < T; u++) {  // the directory entries of the surviving rows
+                    e[u][0] = live[u] & 1u ? map_entry(m, (uint32_t)fk[u].x - m.lo) : 0ull;
+                    e[u][1] = live[u] & 2u ? map_entry(m, (uint32_t)fk[u].y - m.lo) : 0ull;
+                    e[u][2] = live[u] & 4u ? map_entry(m, (uint32_t)fk[u].z - m.lo) : 0ull;
+                    e[u][3] = live[u] & 8u ? map_entry(m, (uint32_t)fk[u].w - m.lo) : 0ull;
+                }
+#pragma unroll
+                for (int u = 0; u < T; u++) {  // live &= hit; the attributes of the rows still joined
+                    const uint32_t d0 = (uint32_t)fk[u].x - m.lo, d1 = (uint32_t)fk[u].y - m.lo, d2 = (uint32_t)fk[u].z - m.lo,
+                                   d3 = (uint32_t)fk[u].w - m.lo;
+                    live[u] &= (uint32_t)map_hit(e[u][0], d0) | ((uint32_t)map_hit(e[u][1], d1) << 1) |
+                               ((uint32_t)map_hit(e[u][2], d2) << 2) | ((uint32_t)map_hit(e[u][3], d3) << 3);
+                    at[u] = make_int4((int)tm.lo, (int)tm.lo, (int)tm.lo, (int)tm.lo);  // of a dropped row: in bounds, never used
+                    if (live[u] & 1u) at[u].x = m.attr[map_rank(e[u][0], d0)];
+                    if (live[u] & 2u) at[u].y = m.attr[map_rank(e[u][1], d1)];
+                    if (live[u] & 4u) at[u].z = m.attr[map_rank(e[u][2], d2)];
+                    if (live[u] & 8u) at[u].w = m.attr[map_rank(e[u][3], d3)];
+                }
+#pragma unroll
+                for (int u = 0; u < T; u++) add_comp(tm, at[u], code[u], in[u]);
+            } else {
+#pragma unroll
+                for (int u = 0; u < T; u++) add_comp(tm, fk[u], code[u], in[u]);  // of a dead row: never read below
+            }
+        }
+        u64 b[T];
+        int4 v[T];
+#pragma unroll
+        for (int u = 0; u < T; u++) {
+            b[u] = __ballot(live[u] != 0u);
+            if (b[u] != 0 && line_live(b[u], lane)) v[u] = load4_nt<VEC>(vals + row + (uint64_t)u * kTileRows);
+        }
+#pragma unroll
+        for (int u = 0; u < T; u++)
+            if (b[u] != 0)  // wave-uniform
+                consume(make_uint4(in[u] & 1u ? code[u].x : kNoSlot, in[u] & 2u ? code[u].y : kNoSlot, in[u] & 4u ? code[u].z : kNoSlot,
+                                   in[u] & 8u ? code[u].w : kNoSlot),
+                        v[u], live[u], b[u]);
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)U * kTileRows <= end; t += (uint64_t)U * kTileRows) tiles(std::integral_constant<int, U>{}, t);
+    for (; t + kTileRows <= end; t += kTileRows) tiles(std::integral_constant<int, 1>{}, t);
+    if (t < end) {  // the column's ragged tile: row by row, none past the end
+        const uint64_t row = t + (uint64_t)tid * 4;
+        const uint32_t live = live_ragged(w, row, end);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (!(live & (1u << i))) continue;
+            uint32_t code = 0;
+            bool joined = true, ok = true;
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                if (!joined) continue;
+                const StarTerm& tm = s.t[j];
+                int comp = tm.col[row + i];
+                if (tm.kind == kStarSet) {
+                    const uint32_t d = (uint32_t)comp - tm.klo;
+                    joined = (star_word(tm, d) >> (d & 31u)) & 1u;
+                    continue;
+                }
+                if (tm.kind == kStarMap) {
+                    const MapArgs m = star_map(tm);
+                    const uint32_t d = (uint32_t)comp - m.lo;
+                    const u64 en = map_entry(m, d);
+                    joined = map_hit(en, d);
+                    if (!joined) continue;
+                    comp = m.attr[map_rank(en, d)];
+                }
+                const uint32_t d = (uint32_t)comp - tm.lo;
+                ok = ok && d <= tm.rm1;
+                code += d * tm.stride;
+            }
+            if (joined) update(ok ? code : kNoSlot, vals[row + i]);
+        }
+    }
+    if (run_open) flush();
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) out.bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * range;
+    for (uint32_t q = tid; q < range; q += kTPB) {
+        out.cnt[base + q] = s_cnt[q];
+        out.sum[base + q] = (long long)s_sum[q];
+        out.mn[base + q] = s_mn[q];
+        out.mx[base + q] = s_mx[q];
+    }
+}
+
+// out[i] = code(row pos[i]) + add for the k joined rows of mq_star_positions (k_group_by_pack_pos'
+// shape: grid-stride, four independent rows a lane in flight): every component read through the
+// positions, where every lookup is a hit. add: 0x80000000 (the sorted column of a tuple, code ^
+// 0x80000000) or, with one component, its lo (the component itself). bad[block][wave] = the rows
+// with a component out of bounds, a lookup that missed or a position outside [0, n)
+// (mq_star_positions writes neither): counted, never used as an address.
+template <int NT>
+__global__ __launch_bounds__(kTPB) void k_group_star_pack_pos(StarArgs s, const int32_t* __restrict__ pos, uint32_t k, uint32_t n,
+                                                              uint32_t add, int32_t* __restrict__ out, uint32_t* __restrict__ bad) {
+    constexpr int kRows = 4;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const u64 stride = (u64)gridDim.x * kTPB;
+    uint32_t nbad = 0;
+    for (u64 i0 = (u64)blockIdx.x * kTPB + tid; i0 < k; i0 += kRows * stride) {
+        uint32_t p[kRows], code[kRows];
+        bool ok[kRows];
+#pragma unroll
+        for (int q = 0; q < kRows; q++) {
+            const u64 i = i0 + q * stride;
+            p[q] = i < k ? (uint32_t)pos[i] : ~0u;
+            ok[q] = p[q] < n;
+            code[q] = 0;
+        }
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const StarTerm& tm = s.t[j];
+            if (tm.kind == kStarSet) continue;  // grid-uniform: no component
+            int c[kRows];
+#pragma unroll
+            for (int q = 0; q < kRows; q++) c[q] = ok[q] ? tm.col[p[q]] : 0;
+            if (tm.kind == kStarMap) {
+                const MapArgs m = star_map(tm);
+                u64 e[kRows];
+#pragma unroll
+                for (int q = 0; q < kRows; q++) e[q] = ok[q] ? map_entry(m, (uint32_t)c[q] - m.lo) : 0ull;
+#pragma unroll
+                for (int q = 0; q < kRows; q++) {
+                    const uint32_t d = (uint32_t)c[q] - m.lo;
+                    ok[q] = ok[q] && map_hit(e[q], d);
+                    c[q] = ok[q] ? m.attr[map_rank(e[q], d)] : 0;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < kRows; q++) {
+                const uint32_t d = (uint32_t)c[q] - tm.lo;
+                ok[q] = ok[q] && d <= tm.rm1;
+                code[q] += d * tm.stride;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kRows; q++) {
+            const u64 i = i0 + q * stride;
+            if (i >= k) continue;
+            nbad += ok[q] ? 0u : 1u;
+            out[i] = (int)(code[q] + add);
+        }
+    }
+    nbad = (uint32_t)wave_sum_u64(nbad);
+    if (lane == 0) bad[(size_t)blockIdx.x * kWaves + (tid >> 6)] = nbad;
+}
+
 // ---- the sort path ----
 
 // ccnt[b] = run heads in block b's chunk of the sorted keys; *groups = their total.
@@ -1554,15 +1868,34 @@ int launch_by_where_dense(const DevState* s, const WhereArgs& w, const ByArgs& a
     return MQ_OK;
 }
 
-// The dense path of the four plans; w: the folded predicates of mq_group_where_plan and
+template <int NT, bool VEC>
+int launch_star_dense(const DevState* s, const WhereArgs& w, const StarArgs& a, const int32_t* vals, uint64_t n, uint32_t range,
+                      void** scratch_out, DenseTabs* tabs, uint32_t* blocks_out, hipStream_t st) {
+    uint32_t g;
+    uint64_t rpb;
+    geometry(s, n, reinterpret_cast<const void*>(&k_group_star_dense<NT, VEC>), &g, &rpb, (uint64_t)star_tiles_in_flight(NT) * kTileRows);
+    void* scratch = pool_alloc(dense_scratch_bytes(g, range));
+    if (!scratch) return set_err(MQ_ENOMEM, "mq_group_star_plan: scratch allocation failed");
+    *tabs = dense_tabs(scratch, g, range);
+    *scratch_out = scratch;
+    *blocks_out = g;
+    hipLaunchKernelGGL((k_group_star_dense<NT, VEC>), dim3(g), dim3(kTPB), 0, st, w, a, vals, n, rpb, range, *tabs);
+    LAUNCHCHK("k_group_star_dense");
+    return MQ_OK;
+}
+
+// The dense path of the plans; w: the folded predicates of mq_group_where_plan and
 // mq_group_by_where_plan (wvec: whether their columns are all 16-byte aligned), or NULL; rows:
 // NULL, or where the sum of the groups' counts goes; by: the nkeys key columns of
 // mq_group_by_plan and mq_group_by_where_plan (keys is not used then), or NULL; jm: the key map
-// of mq_group_join_plan (with w; keys is its foreign key column), or NULL.
+// of mq_group_join_plan (with w; keys is its foreign key column), or NULL; star: the terms of
+// mq_group_star_plan (with w; keys is not used; the table is addressed by the tuple's code, and
+// with one component by component - lo, which is that code), or NULL.
 int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_t* vals, uint64_t n, hipStream_t st,
                const WhereArgs* w = nullptr, bool wvec = false, uint64_t* rows = nullptr, const ByArgs* by = nullptr,
-               int nkeys = 0, const MapArgs* jm = nullptr) {
-    const char* who = jm        ? "mq_group_join_plan"
+               int nkeys = 0, const MapArgs* jm = nullptr, const StarArgs* star = nullptr) {
+    const char* who = star      ? "mq_group_star_plan"
+                      : jm      ? "mq_group_join_plan"
                       : by && w ? "mq_group_by_where_plan"
                       : by      ? "mq_group_by_plan"
                       : w       ? "mq_group_where_plan"
@@ -1575,7 +1908,19 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
     uint32_t blocks = 0;
     const bool vk = aligned16(keys), vv = aligned16(vals);
     int rc;
-    if (by) {
+    if (star) {
+        bool vec = vv && wvec;
+        for (int j = 0; j < star->nterms; j++) vec = vec && aligned16(star->t[j].col);
+        auto launch = [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            return vec ? launch_star_dense<NT, true>(s, *w, *star, vals, n, g->range, &scratch, &tabs, &blocks, st)
+                       : launch_star_dense<NT, false>(s, *w, *star, vals, n, g->range, &scratch, &tabs, &blocks, st);
+        };
+        rc = star->nterms == 1   ? launch(std::integral_constant<int, 1>{})
+             : star->nterms == 2 ? launch(std::integral_constant<int, 2>{})
+             : star->nterms == 3 ? launch(std::integral_constant<int, 3>{})
+                                 : launch(std::integral_constant<int, 4>{});
+    } else if (by) {
         bool vec = vv;
         for (int j = 0; j < nkeys; j++) vec = vec && aligned16(by->keys[j]);
         auto launch = [&](auto nk) {
@@ -1621,6 +1966,7 @@ int plan_dense(const DevState* s, mq_group* g, const int32_t* keys, const int32_
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
     pool_free(d_rows);
     if (rc) return rc;
+    if (h[1] && star) return set_err(MQ_EINVAL, "%s: %llu joined rows with a component outside its bounds", who, h[1]);
     if (h[1] && by) return set_err(MQ_EINVAL, "%s: %llu rows with a key outside its column's bounds", who, h[1]);
     if (h[1]) return set_err(MQ_EINVAL, "%s: %llu %s outside the bounds [%d, %lld]", who, h[1], jm ? "joined attributes" : "keys", g->lo,
                              (long long)g->lo + g->range - 1);
@@ -2112,6 +2458,217 @@ int mq_group_join_plan(const int32_t* const* d_cols, const mq_range* h_ranges, i
             release(g, st);
             return rc;
         }
+        rows = k;
+    }
+    if (h_path) *h_path = g->path;
+    if (h_rows) *h_rows = rows;
+    *h_groups = g->groups;
+    *out = g;
+    return MQ_OK;
+}
+
+int mq_group_star_plan(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const mq_star_term* h_terms, int nterms,
+                       const int32_t* d_vals, uint64_t n, const int32_t* h_key_bounds, int path, mq_group** out,
+                       uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream) {
+    const char* who = "mq_group_star_plan";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (out) *out = nullptr;
+    if (h_groups) *h_groups = 0;
+    if (h_rows) *h_rows = 0;
+    if (nterms < 1 || nterms > MQ_STAR_MAX_TERMS) return set_err(MQ_EINVAL, "%s: nterms %d outside 1..%d", who, nterms, (int)MQ_STAR_MAX_TERMS);
+    if (!out || !h_groups || !h_terms || (ncols > 0 && (!d_cols || !h_ranges))) return set_err(MQ_EINVAL, "%s: NULL pointer", who);
+    int nkeys = 0;
+    for (int j = 0; j < nterms; j++) {
+        if (h_terms[j].km && h_terms[j].ks) return set_err(MQ_EINVAL, "%s: term %d has both a key map and a key set", who, j);
+        nkeys += h_terms[j].ks ? 0 : 1;
+    }
+    if (nkeys < 1 || nkeys > kMaxKeys) return set_err(MQ_EINVAL, "%s: %d components outside 1..%d", who, nkeys, kMaxKeys);
+    if (ncols < 0 || ncols > MQ_WHERE_MAX_COLS)
+        return set_err(MQ_EINVAL, "%s: ncols %d outside 0..%d", who, ncols, (int)MQ_WHERE_MAX_COLS);
+    if (path != MQ_GROUP_AUTO && path != MQ_GROUP_DENSE && path != MQ_GROUP_SORT)
+        return set_err(MQ_EINVAL, "%s: path %d", who, path);
+    if (n >= (1ull << 31)) return set_err(MQ_EINVAL, "%s: n >= 2^31", who);
+    int32_t b[2 * kMaxKeys];
+    uint64_t space = 0;
+    // the bounds given, checked before anything is allocated; bounds the plan finds, after it found them
+    auto check_space = [&]() {
+        if (!by_space(b, nkeys, &space)) return set_err(MQ_EINVAL, "%s: a component's bounds are empty", who);
+        if (space > (1ull << 32))
+            return set_err(MQ_EINVAL, "%s: the key space %llu (saturated at 2^63) is wider than 2^32", who, (u64)space);
+        if (path == MQ_GROUP_DENSE && space > kDenseSlots)
+            return set_err(MQ_EINVAL, "%s: the key space %llu exceeds the dense path's %u slots", who, (u64)space, kDenseSlots);
+        return (int)MQ_OK;
+    };
+    if (n) {
+        for (int c = 0; c < ncols; c++)
+            if (!d_cols[c] || (reinterpret_cast<uintptr_t>(d_cols[c]) & 3u))
+                return set_err(MQ_EINVAL, "%s: column %d NULL or not 4-byte aligned", who, c);
+        for (int j = 0; j < nterms; j++)
+            if (!h_terms[j].d_col || (reinterpret_cast<uintptr_t>(h_terms[j].d_col) & 3u))
+                return set_err(MQ_EINVAL, "%s: term %d: column NULL or not 4-byte aligned", who, j);
+        if (!d_vals || (reinterpret_cast<uintptr_t>(d_vals) & 3u)) return set_err(MQ_EINVAL, "%s: value column NULL or not 4-byte aligned", who);
+        if (h_key_bounds) {
+            for (int j = 0; j < 2 * nkeys; j++) b[j] = h_key_bounds[j];
+            if ((rc = check_space())) return rc;
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    bool none = false;  // an empty map or set among the terms: no row is joined
+    for (int j = 0; j < nterms; j++) {
+        const mq_keyset* ks = h_terms[j].km ? h_terms[j].km->ks : h_terms[j].ks;
+        if (!ks) continue;
+        if (dev != ks->dev)
+            return set_err(MQ_EINVAL, "%s: term %d: the key %s lives on device %d, the call runs on %d", who, j,
+                           h_terms[j].km ? "map" : "set", ks->dev, dev);
+        none = none || ks->lo > ks->hi;
+    }
+    WhereArgs w;
+    bool empty, wvec;
+    fold_ranges(d_cols, h_ranges, ncols, &w, &empty, &wvec);
+    const bool settled = n == 0 || empty || none;
+    if (!settled && !h_key_bounds) {
+        // a map's attributes are known since its build; a plain component costs one pass over its whole column
+        int plain = 0;
+        for (int j = 0; j < nterms; j++) plain += !h_terms[j].km && !h_terms[j].ks;
+        mq_agg a[kMaxKeys] = {};
+        if (plain) {
+            char* ws = static_cast<char*>(pool_alloc(partial_bytes() + kMaxKeys * sizeof(mq_agg)));
+            if (!ws) return set_err(MQ_ENOMEM, "%s: workspace allocation failed", who);
+            mq_agg* d_agg = reinterpret_cast<mq_agg*>(ws + partial_bytes());
+            for (int j = 0, q = 0; j < nterms && !rc; j++)
+                if (!h_terms[j].km && !h_terms[j].ks) rc = mq_reduce(h_terms[j].d_col, n, d_agg + q++, ws, partial_bytes(), stream);
+            if (!rc && hipMemcpyAsync(a, d_agg, plain * sizeof(mq_agg), hipMemcpyDeviceToHost, st) != hipSuccess)
+                rc = set_err(MQ_EHIP, "%s: bounds download failed", who);
+            if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+            pool_free(ws);
+            if (rc) return rc;
+        }
+        for (int j = 0, c = 0, q = 0; j < nterms; j++) {
+            if (h_terms[j].ks) continue;
+            b[2 * c] = h_terms[j].km ? h_terms[j].km->attr_lo : a[q].min;
+            b[2 * c + 1] = h_terms[j].km ? h_terms[j].km->attr_hi : a[q].max;
+            q += h_terms[j].km ? 0 : 1;
+            c++;
+        }
+        if ((rc = check_space())) return rc;
+    }
+    mq_group* g = new (std::nothrow) mq_group();
+    if (!g) return set_err(MQ_ENOMEM, "%s: out of host memory", who);
+    g->dev = dev;
+    g->n = n;
+    g->vals = d_vals;
+    g->stream = st;
+    g->nkeys = nkeys > 1 ? nkeys : 0;  // one component: the one-key handle of mq_group_join_plan
+    g->path = path == MQ_GROUP_SORT ? MQ_GROUP_SORT : MQ_GROUP_DENSE;  // what a plan without rows reports
+    if (settled) {
+        if (h_path) *h_path = g->path;
+        *out = g;
+        return MQ_OK;
+    }
+    auto fail = [&](int code) {
+        release(g, st);
+        return code;
+    };
+    g->path = path != MQ_GROUP_AUTO ? path : space <= kDenseSlots ? MQ_GROUP_DENSE : MQ_GROUP_SORT;
+    // the terms as the kernels take them; the tuple's code as by_args lays it out, kept in the handle for the write
+    StarArgs a = {};
+    a.nterms = nterms;
+    {
+        uint64_t stride = 1;  // up to the key space
+        for (int j = nterms - 1, c = nkeys - 1; j >= 0; j--) {
+            StarTerm& t = a.t[j];
+            const mq_keyset* ks = h_terms[j].km ? h_terms[j].km->ks : h_terms[j].ks;
+            t.col = h_terms[j].d_col;
+            t.kind = h_terms[j].km ? kStarMap : h_terms[j].ks ? kStarSet : kStarPlain;
+            if (ks) {
+                t.bits = ks->bits;
+                t.klo = (uint32_t)ks->lo;
+                t.kwm1 = (uint32_t)ks->hi - (uint32_t)ks->lo;
+            }
+            if (h_terms[j].km) {
+                t.dir = h_terms[j].km->dir;
+                t.attr = h_terms[j].km->attr;
+            }
+            if (h_terms[j].ks) continue;
+            t.lo = (uint32_t)b[2 * c];
+            t.rm1 = (uint32_t)((int64_t)b[2 * c + 1] - (int64_t)b[2 * c]);
+            t.stride = (uint32_t)stride;
+            if (nkeys > 1) {
+                g->klo[c] = b[2 * c];
+                g->krm1[c] = t.rm1;
+                g->kstride[c] = t.stride;
+            }
+            stride *= (uint64_t)t.rm1 + 1;
+            c--;
+        }
+    }
+    uint64_t rows = 0;
+    if (g->path == MQ_GROUP_DENSE) {
+        g->lo = nkeys > 1 ? 0 : b[0];  // the table is addressed by the code; one component's code is component - lo
+        g->range = (uint32_t)space;
+        rc = plan_dense(s, g, nullptr, d_vals, n, st, &w, wvec, h_rows ? &rows : nullptr, nullptr, 0, nullptr, &a);
+        if (rc) return fail(rc);
+    } else {
+        // the K joined rows' positions, their codes packed through them, their values, then the sort path
+        const size_t ws_bytes = mq_semi_workspace_bytes(n);
+        void* ws = pool_alloc(ws_bytes);
+        int32_t* pos = static_cast<int32_t*>(pool_alloc(n * 4));
+        u64* d_k = static_cast<u64*>(pool_alloc(sizeof(u64)));
+        u64 k = 0;
+        rc = ws && pos && d_k ? MQ_OK : set_err(MQ_ENOMEM, "%s: allocation failed", who);
+        if (!rc)
+            rc = mq_star_positions(d_cols, h_ranges, ncols, h_terms, nterms, nullptr, n, pos, reinterpret_cast<uint64_t*>(d_k), ws,
+                                   ws_bytes, stream);
+        if (!rc && hipMemcpyAsync(&k, d_k, sizeof k, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = set_err(MQ_EHIP, "%s: count download failed", who);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+        pool_free(d_k);
+        pool_free(ws);
+        int32_t* packed = nullptr;
+        uint32_t* bad = nullptr;
+        u64* d_total = nullptr;
+        if (!rc && k) {
+            packed = static_cast<int32_t*>(pool_alloc(k * 4));
+            g->own_vals = static_cast<int32_t*>(pool_alloc(k * 4));
+            d_total = static_cast<u64*>(pool_alloc(sizeof(u64)));
+            const uint32_t grid = stream_grid(s, (k + 3) / 4);  // four rows a lane in flight
+            bad = static_cast<uint32_t*>(pool_alloc((size_t)grid * kWaves * 4));
+            if (!packed || !g->own_vals || !d_total || !bad) rc = set_err(MQ_ENOMEM, "%s: allocation failed", who);
+            if (!rc) rc = mq_fetch(d_vals, pos, k, g->own_vals, stream);
+            if (!rc) {
+                const uint32_t add = nkeys > 1 ? 0x80000000u : (uint32_t)b[0];
+                auto launch = [&](auto nt) {
+                    constexpr int NT = decltype(nt)::value;
+                    hipLaunchKernelGGL((k_group_star_pack_pos<NT>), dim3(grid), dim3(kTPB), 0, st, a, pos, (uint32_t)k, (uint32_t)n, add,
+                                       packed, bad);
+                };
+                if (nterms == 1) launch(std::integral_constant<int, 1>{});
+                else if (nterms == 2) launch(std::integral_constant<int, 2>{});
+                else if (nterms == 3) launch(std::integral_constant<int, 3>{});
+                else launch(std::integral_constant<int, 4>{});
+                hipLaunchKernelGGL(k_group_by_bad, dim3(1), dim3(kTPB), 0, st, bad, grid * kWaves, d_total);
+                if (hipGetLastError() != hipSuccess) rc = set_err(MQ_EHIP, "launch of k_group_star_pack_pos / k_group_by_bad failed");
+            }
+            u64 total = 0;
+            if (!rc && hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, st) != hipSuccess)
+                rc = set_err(MQ_EHIP, "%s: count download failed", who);
+            if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+            if (!rc && total) rc = set_err(MQ_EINVAL, "%s: %llu joined rows with a component outside its bounds", who, total);
+        }
+        pool_free(bad);
+        pool_free(d_total);
+        pool_free_on(pos, st);  // the gather and the pack queued above are its last readers
+        if (!rc && k) {
+            g->vals = g->own_vals;
+            g->n = k;
+            rc = plan_sort(g, packed, k, nullptr, st);  // synchronises
+        }
+        pool_free_on(packed, st);
+        if (rc) return fail(rc);
         rows = k;
     }
     if (h_path) *h_path = g->path;

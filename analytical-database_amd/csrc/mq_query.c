@@ -1569,6 +1569,92 @@ Result** group_aggregate_by_where(GeneralizedColumn** columns, int** lows, int**
     return group_results(who, g, groups, nkeys, rc, ret_status);
 }
 
+/* group_aggregate_by over the fact rows for which every range holds and every joined dimension
+ * has the row's foreign key, grouped by the tuple of the dimensions' attributes and the plain
+ * fact columns among the terms (no reference counterpart). Every key map and
+ * key set is built per call and freed before returning, on every path. */
+Result** group_aggregate_star(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn** fkeys,
+                              GeneralizedColumn** dim_keys, GeneralizedColumn** dim_attrs, int nterms,
+                              GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "group_aggregate_star";
+    if (nterms < 1 || nterms > MQ_STAR_MAX_TERMS) {
+        dml_fail(ret_status, who, "nterms outside 1..4");
+        return NULL;
+    }
+    if (!fkeys || !dim_keys || !dim_attrs) {
+        dml_fail(ret_status, who, "fkeys, dim_keys and dim_attrs must each hold nterms entries");
+        return NULL;
+    }
+    int nkeys = 0;
+    for (int t = 0; t < nterms; t++) {
+        if (!dim_keys[t] && dim_attrs[t]) {
+            dml_fail(ret_status, who, "a term with dim_attrs needs dim_keys");
+            return NULL;
+        }
+        nkeys += !dim_keys[t] || dim_attrs[t];
+    }
+    if (nkeys < 1 || nkeys > MQ_GROUP_MAX_KEYS) {
+        dml_fail(ret_status, who, "the terms must give 1..4 group keys");
+        return NULL;
+    }
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t* dk[MQ_STAR_MAX_TERMS];
+    const int32_t* dv = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    mq_star_term terms[MQ_STAR_MAX_TERMS] = {{0}};
+    mq_keymap* km[MQ_STAR_MAX_TERMS] = {0};
+    mq_keyset* ks[MQ_STAR_MAX_TERMS] = {0};
+    size_t n = 0;
+    Result** out = NULL;
+    for (int t = 0; t < nterms; t++) { /* the dimensions first: each build synchronises */
+        if (!dim_keys[t]) continue;
+        if (!dim_attrs[t]) {
+            if (in_keyset(who, dim_keys[t], &ks[t], ret_status)) goto done;
+            continue;
+        }
+        const int32_t *ddk = NULL, *dda = NULL;
+        size_t n1 = 0, n1a = 0;
+        const int a = gcol_device(dim_keys[t], &ddk, &n1, ret_status);
+        if (a > 0) goto done;
+        const int b = a < 0 ? a : gcol_device(dim_attrs[t], &dda, &n1a, ret_status);
+        if (b > 0) goto done;
+        if (a < 0 || b < 0 || n1 != n1a || n1 >= ((size_t)1 << 31)) {
+            dml_fail(ret_status, who,
+                     a < 0 || b < 0 ? "dim_keys and dim_attrs must each be a Column or an INT Result"
+                     : n1 != n1a    ? "dim_keys and dim_attrs differ in length"
+                                    : "2^31 dimension rows or more");
+            goto done;
+        }
+        const int rc = mq_keymap_build(ddk, dda, n1, 0, 0, 0, &km[t], NULL, g_stream); /* synchronises */
+        if (rc) {
+            fail(ret_status, who, rc);
+            goto done;
+        }
+    }
+    {
+        const int a = by_keys(fkeys, nterms, dk, &n, 0, ret_status);
+        if (a) {
+            if (a < 0) dml_fail(ret_status, who, a == -1 ? "every fkeys entry must be a Column or an INT Result" : "the fkeys differ in length");
+            goto done;
+        }
+        if (where_args_from(who, 0, 1, columns, lows, highs, ncols, values, d_cols, ranges, &dv, &n, ret_status)) goto done;
+        for (int t = 0; t < nterms; t++) terms[t] = (mq_star_term){dk[t], km[t], ks[t]};
+        mq_group* g = NULL;
+        uint64_t groups = 0;
+        const int rc = mq_group_star_plan(d_cols, ranges, ncols, terms, nterms, dv, n, NULL, MQ_GROUP_AUTO, &g, &groups, NULL, NULL,
+                                          g_stream);
+        out = group_results(who, g, groups, nkeys, rc, ret_status);
+    }
+done:
+    mq_stream_sync(g_stream);
+    for (int t = 0; t < nterms; t++) {
+        mq_keymap_free(km[t]);
+        mq_keyset_free(ks[t]);
+    }
+    return out;
+}
+
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner
  * ascending — exactly a hash join that builds on the inner side (insertion
  * order = inner order) and probes with the outer side, outputs swapped. */

@@ -36,7 +36,8 @@
 //
 // mq_semi_positions / mq_semi_agg put a key [NOT] IN set predicate behind
 // the ranges in the same stream: k_semi_mask and k_semi_agg, further down, with the scan and
-// k_where_expand shared.
+// k_where_expand shared. mq_star_positions puts up to four such predicates
+// there, one per key map or key set of a star query's terms: k_star_mask, global bitmap only.
 
 #include <hip/hip_runtime.h>
 
@@ -416,6 +417,93 @@ __global__ __launch_bounds__(kTPB, 4) void k_semi_agg(WhereArgs a, SemiArgs k, c
     }
 }
 
+// ---- ranges AND every km / ks term of a star query (mq_star_positions) ----
+// k_semi_mask with one key predicate per term, in the order given: before each term the tiles
+// are balloted again, only the surviving 128-byte lines of the term's column are requested, and
+// the bitmap word is loaded for surviving rows only (a plain cached load; for a key map the
+// map's own key set bitmap, not its directory). The global bitmap only: there is no LDS form.
+// `s` holds the filtering terms alone; none at all leaves the ranges (or, without any, every row).
+
+template <bool VEC, int U>
+__device__ __forceinline__ void star_tiles(const WhereArgs& a, const StarArgs& s, uint64_t row, int lane, uint32_t (&live)[U]) {
+    live_tiles<VEC, U>(a, row, lane, live);
+    for (int j = 0; j < s.nterms; j++) {
+        const StarTerm& tm = s.t[j];
+        int4 v[U];
+        uint32_t w[U][4];
+        u64 any = 0;
+        const int32_t* __restrict__ p = tm.col + row;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const u64 b = __ballot(live[u] != 0u);
+            any |= b;
+            v[u] = make_int4(0, 0, 0, 0);
+            if (b != 0 && line_live(b, lane)) v[u] = load4_nt<VEC>(p + (uint64_t)u * kTileRows);
+        }
+        if (any == 0) break;  // wave-uniform: nothing left in the iteration
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            w[u][0] = live[u] & 1u ? star_word(tm, (uint32_t)v[u].x - tm.klo) : 0u;
+            w[u][1] = live[u] & 2u ? star_word(tm, (uint32_t)v[u].y - tm.klo) : 0u;
+            w[u][2] = live[u] & 4u ? star_word(tm, (uint32_t)v[u].z - tm.klo) : 0u;
+            w[u][3] = live[u] & 8u ? star_word(tm, (uint32_t)v[u].w - tm.klo) : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            live[u] &= ((w[u][0] >> (((uint32_t)v[u].x - tm.klo) & 31u)) & 1u) | (((w[u][1] >> (((uint32_t)v[u].y - tm.klo) & 31u)) & 1u) << 1) |
+                       (((w[u][2] >> (((uint32_t)v[u].z - tm.klo) & 31u)) & 1u) << 2) |
+                       (((w[u][3] >> (((uint32_t)v[u].w - tm.klo) & 31u)) & 1u) << 3);
+    }
+}
+
+// The ragged tile, row by row.
+__device__ __forceinline__ uint32_t star_ragged(const WhereArgs& a, const StarArgs& s, uint64_t row, uint64_t end) {
+    uint32_t live = live_ragged(a, row, end);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        if (!(live & (1u << e))) continue;
+        for (int j = 0; j < s.nterms; j++) {
+            const uint32_t d = (uint32_t)s.t[j].col[row + e] - s.t[j].klo;
+            if (!((star_word(s.t[j], d) >> (d & 31u)) & 1u)) {
+                live &= ~(1u << e);
+                break;
+            }
+        }
+    }
+    return live;
+}
+
+// k_where_mask's ballot words and counts, with the terms behind the ranges.
+template <bool VEC>
+__global__ __launch_bounds__(kTPB, 4) void k_star_mask(WhereArgs a, StarArgs s, uint64_t n, uint64_t rows_per_block,
+                                                       u64* __restrict__ bm, uint32_t* __restrict__ cnt) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t start = (uint64_t)blockIdx.x * rows_per_block;
+    uint64_t end = start + rows_per_block;
+    if (end > n) end = n;
+
+    auto put = [&](uint64_t t, uint32_t live) {
+        const u64 w0 = __ballot(live & 1u), w1 = __ballot(live & 2u), w2 = __ballot(live & 4u), w3 = __ballot(live & 8u);
+        const uint64_t wt = t / kWaveRows + (uint64_t)wave;
+        if (lane < 4) bm[wt * 4 + lane] = lane == 0 ? w0 : lane == 1 ? w1 : lane == 2 ? w2 : w3;
+        if (lane == 0) cnt[wt] = (uint32_t)(__popcll(w0) + __popcll(w1) + __popcll(w2) + __popcll(w3));
+    };
+
+    uint64_t t = start;
+    for (; t + (uint64_t)kWhU * kTileRows <= end; t += (uint64_t)kWhU * kTileRows) {
+        uint32_t live[kWhU];
+        star_tiles<VEC, kWhU>(a, s, t + (uint64_t)tid * 4, lane, live);
+#pragma unroll
+        for (int u = 0; u < kWhU; u++) put(t + (uint64_t)u * kTileRows, live[u]);
+    }
+    for (; t + kTileRows <= end; t += kTileRows) {
+        uint32_t live[1];
+        star_tiles<VEC, 1>(a, s, t + (uint64_t)tid * 4, lane, live);
+        put(t, live[0]);
+    }
+    if (t < end) put(t, star_ragged(a, s, t + (uint64_t)tid * 4, end));  // block-uniform
+}
+
 // The aggregate over no rows, in the stream's order.
 __global__ void k_where_empty(mq_agg* __restrict__ out) {
     if (threadIdx.x || blockIdx.x) return;
@@ -476,8 +564,9 @@ int allow_lds(const void* fn, size_t bytes) {
 
 // The positions of the rows that `a` (and the key predicate `k`, when given) leave: the mask
 // kernel, the scan and the expansion, on a checked workspace. lds: k's bitmap goes to LDS.
+// star (without k): the filtering terms of mq_star_positions behind the ranges.
 int run_positions(DevState* s, const WhereArgs& a, bool vec, const SemiArgs* k, bool lds, const int32_t* d_payload, uint64_t n,
-                  int32_t* d_pos_out, uint64_t* d_count, void* d_ws, hipStream_t st) {
+                  int32_t* d_pos_out, uint64_t* d_count, void* d_ws, hipStream_t st, const StarArgs* star = nullptr) {
     const Layout l = layout(n);
     char* ws = static_cast<char*>(d_ws);
     u64* bm = reinterpret_cast<u64*>(ws + l.bm);
@@ -487,7 +576,15 @@ int run_positions(DevState* s, const WhereArgs& a, bool vec, const SemiArgs* k, 
     uint64_t rpb;
     int rc;
     HIPCHK(hipMemsetAsync(cnt + l.nwt, 0, sizeof(uint32_t), st));  // the scan's last input (its output is K)
-    if (!k) {
+    if (star) {
+        geometry(s, n, vec ? reinterpret_cast<const void*>(&k_star_mask<true>) : reinterpret_cast<const void*>(&k_star_mask<false>),
+                 &g, &rpb, (uint64_t)kWhU * kTileRows);
+        if (vec)
+            hipLaunchKernelGGL((k_star_mask<true>), dim3(g), dim3(kTPB), 0, st, a, *star, n, rpb, bm, cnt);
+        else
+            hipLaunchKernelGGL((k_star_mask<false>), dim3(g), dim3(kTPB), 0, st, a, *star, n, rpb, bm, cnt);
+        LAUNCHCHK("k_star_mask");
+    } else if (!k) {
         geometry(s, n, vec ? reinterpret_cast<const void*>(&k_where_mask<true>) : reinterpret_cast<const void*>(&k_where_mask<false>),
                  &g, &rpb, (uint64_t)kWhU * kTileRows);
         if (vec)
@@ -657,6 +754,54 @@ int mq_semi_positions(const int32_t* const* d_cols, const mq_range* h_ranges, in
     // NOT IN the empty set: the ranges alone, as mq_where_positions runs them
     if (trivial) return run_positions(s, a, vec, nullptr, false, d_payload, n, d_pos_out, d_count, d_ws, st);
     return run_positions(s, a, vec, &k, lds, d_payload, n, d_pos_out, d_count, d_ws, st);
+}
+
+int mq_star_positions(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const mq_star_term* h_terms, int nterms,
+                      const int32_t* d_payload, uint64_t n, int32_t* d_pos_out, uint64_t* d_count, void* d_ws, size_t ws_bytes,
+                      void* stream) {
+    const char* who = "mq_star_positions";
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (!d_count) return set_err(MQ_EINVAL, "%s: NULL count", who);
+    if (nterms < 1 || nterms > MQ_STAR_MAX_TERMS) return set_err(MQ_EINVAL, "%s: nterms %d outside 1..%d", who, nterms, (int)MQ_STAR_MAX_TERMS);
+    if (!h_terms) return set_err(MQ_EINVAL, "%s: NULL terms", who);
+    if (n && (!d_pos_out || (reinterpret_cast<uintptr_t>(d_pos_out) & 3u)))
+        return set_err(MQ_EINVAL, "%s: output NULL or not 4-byte aligned", who);
+    WhereArgs a;
+    bool empty, vec;
+    if ((rc = prepare(who, 0, d_cols, h_ranges, ncols, d_payload, false, n, d_ws, ws_bytes, &a, &empty, &vec))) return rc;
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    StarArgs sa = {};
+    bool none = false;  // an empty map or set: no row is joined
+    for (int j = 0; j < nterms; j++) {
+        const mq_star_term& t = h_terms[j];
+        if (t.km && t.ks) return set_err(MQ_EINVAL, "%s: term %d has both a key map and a key set", who, j);
+        if (n && (!t.d_col || (reinterpret_cast<uintptr_t>(t.d_col) & 3u)))
+            return set_err(MQ_EINVAL, "%s: term %d: column NULL or not 4-byte aligned", who, j);
+        const mq_keyset* ks = t.km ? t.km->ks : t.ks;
+        if (!ks) continue;  // a plain term places no condition
+        if (dev != ks->dev) return set_err(MQ_EINVAL, "%s: term %d: the key %s lives on device %d, the call runs on %d", who, j,
+                                           t.km ? "map" : "set", ks->dev, dev);
+        if (ks->lo > ks->hi) {
+            none = true;
+            continue;
+        }
+        StarTerm& o = sa.t[sa.nterms++];
+        o.col = t.d_col;
+        o.bits = ks->bits;
+        o.klo = (uint32_t)ks->lo;
+        o.kwm1 = (uint32_t)ks->hi - (uint32_t)ks->lo;
+        o.kind = kStarSet;
+        vec = vec && aligned16(t.d_col);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0 || empty || none) {
+        HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+        return MQ_OK;
+    }
+    return run_positions(s, a, vec, nullptr, false, d_payload, n, d_pos_out, d_count, d_ws, st, &sa);
 }
 
 int mq_semi_agg(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols, const int32_t* d_key, const mq_keyset* ks,

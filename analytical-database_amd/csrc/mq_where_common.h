@@ -3,7 +3,8 @@
 // mq_group.hip): the folded predicates as kernel arguments, a lane's surviving rows per
 // tile with the dead 128-byte lines of the later columns skipped, and the host's fold; the
 // key set that mq_keyset.hip builds and mq_where.hip's semi-join kernels probe; and the key
-// map that mq_keymap.hip builds on it and k_group_join_dense in mq_group.hip looks up.
+// map that mq_keymap.hip builds on it and k_group_join_dense in mq_group.hip looks up; and the
+// terms of a star query (k_star_mask in mq_where.hip, k_group_star_dense in mq_group.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -112,6 +113,37 @@ __device__ __forceinline__ bool map_hit(unsigned long long e, uint32_t d) { retu
 __device__ __forceinline__ uint32_t map_rank(unsigned long long e, uint32_t d) {
     return (uint32_t)(e >> 32) + (uint32_t)__popc((uint32_t)e & ((1u << (d & 31u)) - 1u));
 }
+
+// One term of a star query (mq_star_positions, mq_group_star_plan) as kernel arguments: a fact
+// column and what its value means. kStarSet: the row is kept when the value is in the key set
+// `bits` over [klo, klo + kwm1] (SemiArgs' lookup); no component. kStarMap: the row is kept when
+// the value is a key of the map (MapArgs' lookup on dir / attr; `bits` is the map's own key set
+// bitmap, which the mask kernel probes instead of the directory) and its attribute is the
+// component. kStarPlain: no condition, the value is the component. A component c adds
+// (c - lo) * stride to the row's tuple code and is in bounds when (uint32)(c - lo) <= rm1
+// (ByArgs' rule, per component).
+enum : uint32_t { kStarPlain = 0, kStarMap = 1, kStarSet = 2 };
+
+struct StarTerm {
+    const int32_t* col;
+    const uint32_t* bits;
+    const unsigned long long* dir;
+    const int32_t* attr;
+    uint32_t klo, kwm1;
+    uint32_t lo, rm1, stride;
+    uint32_t kind;
+};
+
+struct StarArgs {
+    StarTerm t[MQ_STAR_MAX_TERMS];
+    int nterms;
+};
+
+// The term's map as MapArgs (map_entry, map_hit and map_rank serve it).
+__device__ __forceinline__ MapArgs star_map(const StarTerm& t) { return MapArgs{t.col, t.dir, t.attr, t.klo, t.kwm1}; }
+
+// The bitmap word of offset d, or 0 (no bit set) for a key outside the span.
+__device__ __forceinline__ uint32_t star_word(const StarTerm& t, uint32_t d) { return d <= t.kwm1 ? t.bits[d >> 5] : 0u; }
 
 // The host's fold of ncols checked (column, range) pairs into *a. A range that matches
 // every int32 drops out (its column is not read). *empty: some range matches no int32 (*a

@@ -29,6 +29,7 @@ MQ_TOPK_AUTO, MQ_TOPK_SELECT, MQ_TOPK_SORT = 0, 1, 2
 MQ_TOPK_SORT_DIV = 4
 MQ_WHERE_MAX_COLS = 8
 MQ_SEMI_AUTO, MQ_SEMI_LDS, MQ_SEMI_GLOBAL = 0, 1, 2
+MQ_STAR_MAX_TERMS = 4
 MQ_JOIN_STATE_WORDS = 3  # include/mq_device.h mq_join_state
 (MQ_JOIN_STATE_PART, MQ_JOIN_STATE_DUPW, MQ_JOIN_STATE_PACKED, MQ_JOIN_STATE_RS, MQ_JOIN_STATE_PRUNS,
  MQ_JOIN_STATE_RUN2, MQ_JOIN_STATE_DEFERRED, MQ_JOIN_STATE_ROW_WRITE) = (1 << b for b in range(8))
@@ -55,6 +56,10 @@ class MqKeysetInfo(C.Structure):  # include/mq_device.h mq_keyset_info
 class MqKeymapInfo(C.Structure):  # include/mq_device.h mq_keymap_info
     _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("attr_lo", C.c_int32), ("attr_hi", C.c_int32),
                 ("entries", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class MqStarTerm(C.Structure):  # include/mq_device.h mq_star_term
+    _fields_ = [("d_col", C.c_void_p), ("km", C.c_void_p), ("ks", C.c_void_p)]
 
 
 class ColumnIndex(C.Structure):
@@ -239,6 +244,10 @@ _SIGS = {
     "mq_keymap_free": (_int, [_vp]),
     "mq_group_join_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _vp, _vp, _u64, _vp, _int, C.POINTER(_vp),
                                   C.POINTER(_u64), C.POINTER(_int), C.POINTER(_u64), _vp]),
+    "mq_star_positions": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, C.POINTER(MqStarTerm), _int, _vp, _u64, _vp, _vp, _vp,
+                                 _sz, _vp]),
+    "mq_group_star_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, C.POINTER(MqStarTerm), _int, _vp, _u64, _vp, _int,
+                                  C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_int), C.POINTER(_u64), _vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -300,6 +309,10 @@ _SIGS = {
                                               C.POINTER(C.POINTER(_int)), _int, C.POINTER(GeneralizedColumn),
                                               C.POINTER(GeneralizedColumn), C.POINTER(GeneralizedColumn),
                                               C.POINTER(GeneralizedColumn), _PS]),
+    "group_aggregate_star": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                                              C.POINTER(C.POINTER(_int)), _int, C.POINTER(C.POINTER(GeneralizedColumn)),
+                                              C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(GeneralizedColumn)),
+                                              _int, C.POINTER(GeneralizedColumn), _PS]),
     "group_aggregate_by": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), _int, C.POINTER(GeneralizedColumn),
                                             _PS]),
     "group_aggregate_by_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),

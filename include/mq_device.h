@@ -786,6 +786,76 @@ int mq_group_join_plan(const int32_t* const* d_cols, const mq_range* h_ranges, i
                        const int32_t* h_attr_bounds /* NULL: the map's attr_lo, attr_hi */, int path,
                        mq_group** out, uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream);
 
+/* ---- GROUP BY over several joined dimensions, in one pass ----
+ *   SELECT d1.a, d2.b, f.k, count(*), sum(f.v), min(f.v), max(f.v)
+ *   FROM f JOIN d1 ON f.k1 = d1.key JOIN d2 ON f.k2 = d2.key [JOIN d3 ... only as a filter]
+ *   WHERE f.c0 IN [..) AND ... GROUP BY d1.a, d2.b, f.k
+ * A term is a fact column and what it means (mq_star_term): with `km`, the column is a foreign
+ * key into that key map, the row is kept when the key has a partner, and the partner's attribute
+ * is a component of the group tuple; with `ks`, the row is kept when the value is in that key set
+ * and the term gives no component (a dimension joined only as a filter); with neither, the value
+ * itself is a component (a fact-side group key). Both set is MQ_EINVAL. nkeys = the terms without
+ * `ks`, 1..MQ_GROUP_MAX_KEYS.
+ * Row i is JOINED when every range holds (mq_where_positions' meaning; ncols == 0: every row,
+ * d_cols and h_ranges may then be NULL) and every km / ks term finds d_col[i]. Its tuple is the
+ * components of the non-ks terms in the order given, the first most significant.
+ * mq_group_star_plan: the result is exactly mq_group_by_plan over the joined rows' tuples and
+ *        values: one entry per distinct tuple in ascending lexicographic signed order, uint64_t
+ *        count, exact int64_t sum, min and max. Integer operations only: bitwise the same
+ *        whatever the path, the grid, the alignment, the order of the ranges, or the place of
+ *        the ks terms among the others. *h_rows (may be NULL) = the joined rows. The handle is an
+ *        ordinary mq_group: with nkeys == 1 exactly what mq_group_join_plan leaves (mq_group_write
+ *        writes the component), with nkeys > 1 what mq_group_by_plan leaves (mq_group_by_write).
+ *        Shapes that the older plans could serve are not handed to them.
+ * bounds: h_key_bounds is {lo_0, hi_0, ..} per component, inclusive, and constrains JOINED rows
+ *        only: a joined row's component outside its own bounds is MQ_EINVAL with everything
+ *        released, and is never used as an address (every component is checked by itself, not the
+ *        summed code). With NULL, a km component takes the map's attr_lo / attr_hi at no cost,
+ *        and a plain component takes one mq_reduce over its WHOLE column: all n rows, joined or
+ *        not, so a stray value in a dropped row widens the key space (and may move the plan to
+ *        the sort path or past 2^32). Bounds from the caller avoid that pass. P = prod(hi_j -
+ *        lo_j + 1) picks the path as in mq_group_by_plan; MQ_GROUP_DENSE forced past
+ *        mq_group_dense_slots(), or P > 2^32, is MQ_EINVAL.
+ * order: the ranges run first, in the order given, then the terms in the order given. Of each
+ *        term's column only the 128-byte lines that still hold a row are requested, and a lookup
+ *        is made for surviving rows only: put the most selective filter first, as for
+ *        mq_where_positions.
+ * dense: one streaming pass, k_group_star_dense: per term the surviving lines of its column
+ *        (non-temporal), then the set's bitmap word, or the map's directory entry and for hits the
+ *        attribute (plain cached loads, global memory only: there is no LDS form of the lookups);
+ *        the tuple code addresses k_group_by_where_dense's per-block LDS tables.
+ * sort:  mq_star_positions gives the K joined rows; k_group_star_pack_pos reads every component
+ *        through them and writes the codes, mq_fetch gathers the values into a buffer the handle
+ *        owns, then mq_group_plan's sort path runs on the codes.
+ * Settled on the host with no launch over the columns: n == 0, a range that no int32 satisfies,
+ * an empty map or set among the terms: MQ_OK, zero groups and a handle to free.
+ * MQ_EINVAL with nothing allocated: nterms outside 1..MQ_STAR_MAX_TERMS, nkeys outside
+ * 1..MQ_GROUP_MAX_KEYS (terms that are all ks), km and ks in one term, a map or set of another
+ * device; pointer, ncols (0..8 here), n and path rules are mq_group_by_where_plan's. Synchronises.
+ * mq_star_positions: mq_semi_positions with the conjunction of all km / ks terms behind the
+ *        ranges (a plain term places no condition; nterms 1..MQ_STAR_MAX_TERMS):
+ *        d_payload ? d_payload[i] : i of every joined row, ascending i, and their number K in
+ *        *d_count. Workspace mq_semi_workspace_bytes(n), 16-byte aligned; asynchronous on
+ *        `stream`; nothing is written at or past entry K. k_star_mask probes the global bitmap
+ *        (for a km term the map's own key set bitmap, 4-byte words, not the directory); there is
+ *        no LDS form. n == 0, an unsatisfiable range or an empty map or set write K = 0.
+ * Not measured on a device yet (tools/bench_star.py is the sweep). */
+enum { MQ_STAR_MAX_TERMS = 4 };
+typedef struct mq_star_term {          /* 24 bytes */
+    const int32_t*   d_col;            /* a fact column, n rows */
+    const mq_keymap* km;               /* grouped through a dimension: component = attribute of d_col[i] in km */
+    const mq_keyset* ks;               /* filter only: row kept when d_col[i] is in ks; no component */
+} mq_star_term;                        /* km == ks == NULL: d_col[i] itself is the component; both set: MQ_EINVAL */
+int mq_star_positions(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols /* 0..8 */,
+                      const mq_star_term* h_terms, int nterms /* 1..4 */,
+                      const int32_t* d_payload /* may be NULL */, uint64_t n,
+                      int32_t* d_pos_out, uint64_t* d_count /* device */, void* d_ws, size_t ws_bytes, void* stream);
+int mq_group_star_plan(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols /* 0..8 */,
+                       const mq_star_term* h_terms, int nterms /* 1..4 */,
+                       const int32_t* d_vals, uint64_t n,
+                       const int32_t* h_key_bounds /* NULL or 2*nkeys host ints */, int path,
+                       mq_group** out, uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

@@ -437,6 +437,39 @@ Result** group_aggregate_join(GeneralizedColumn** columns, int** lows, int** hig
                               GeneralizedColumn* fkeys, GeneralizedColumn* dim_keys,
                               GeneralizedColumn* dim_attrs, GeneralizedColumn* values, Status* ret_status);
 
+/* ---- GROUP BY over several joined dimensions (not in the reference) ----
+ * group_aggregate_star: SELECT d1.a, d2.b, f.k, count(*), sum(f.v), min(f.v), max(f.v) FROM f
+ * JOIN d1 ON f.k1 = d1.key JOIN d2 ON f.k2 = d2.key [JOIN d3 ... only as a filter] WHERE f.c0 IN
+ * [..) AND ... GROUP BY d1.a, d2.b, f.k in one operator (mq_group_star_plan in
+ * mq_device.h). `columns`, `lows`, `highs` and `ncols` are group_aggregate_join's. `fkeys`,
+ * `dim_keys` and `dim_attrs` each hold `nterms` (1..4) entries; term t is fkeys[t], a fact
+ * column, and
+ *   dim_keys[t] == NULL (dim_attrs[t] must be NULL too): fkeys[t] itself is a group key;
+ *   dim_keys[t] and dim_attrs[t]: a dimension, joined on fkeys[t] = dim_keys[t], whose attribute
+ *       is a group key (a key map built per call; dim_keys[t] holds every key once);
+ *   dim_keys[t] alone: a dimension joined only as a filter (a key set built per call): the row
+ *       is kept when fkeys[t] is among dim_keys[t]; no group key.
+ * The terms must give nkeys = 1..4 group keys, in the order of the terms, the first most
+ * significant. Every fkeys entry and `values` are a COLUMN or an INT RESULT as long as the
+ * columns; dim_keys[t] and dim_attrs[t] are a COLUMN or an INT RESULT, equally long (below 2^31).
+ * A fact row whose key has no partner in some dimension is dropped (inner joins); an empty
+ * dimension gives empty Results and OK. Returns group_aggregate_by's nkeys + 4 Results under its
+ * ownership and shadow rules (with nkeys == 1 group_aggregate's five): the key columns (INT) in
+ * the order of the terms, then counts (LONG), sums (LONG), minima (INT), maxima (INT), one tuple
+ * per distinct key tuple with a joined row, ascending lexicographically. The ranges run first,
+ * then the terms in the order given: put the most selective first. Every map and set is freed
+ * before returning, on every path. No key bounds are passed: a dimension's attribute range is
+ * known from its map, and a plain group key costs one more read of its whole column. Runs on
+ * the calling device; a column held as row shards drops them and is split again on next use.
+ * ERROR and NULL (a "libmq:" line on stderr): no device, ncols outside 0..8, nterms outside
+ * 1..4, no or more than four group keys, dim_attrs without dim_keys, an argument of the wrong
+ * kind, different lengths, 2^31 rows or more, a key that occurs twice in a mapped dim_keys[t], a
+ * key space wider than 2^32, a device failure. Not measured on a device yet. */
+Result** group_aggregate_star(GeneralizedColumn** columns, int** lows, int** highs, int ncols /* 0..8 */,
+                              GeneralizedColumn** fkeys, GeneralizedColumn** dim_keys,
+                              GeneralizedColumn** dim_attrs, int nterms /* 1..4 */,
+                              GeneralizedColumn* values, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
