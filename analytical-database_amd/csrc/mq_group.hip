@@ -113,6 +113,7 @@
 
 #include "mq_common.h"
 #include "mq_device.h"
+#include "mq_group_impl.h"
 #include "mq_scan_common.h"
 #include "mq_where_common.h"
 
@@ -2134,6 +2135,47 @@ void release(mq_group* g, hipStream_t st) {
 }
 
 }  // namespace
+
+// What mq_measures.hip shares (mq_group_impl.h): the kernels above stay this unit's own.
+namespace mqi {
+
+bool group_key_space(const int32_t* b, int nkeys, uint64_t* space) { return by_space(b, nkeys, space); }
+
+void group_launch_star_pack_pos(const StarArgs& a, uint32_t grid, const int32_t* pos, uint32_t k, uint32_t n, uint32_t add,
+                                int32_t* packed, uint32_t* bad, hipStream_t st) {
+    auto launch = [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((k_group_star_pack_pos<NT>), dim3(grid), dim3(kTPB), 0, st, a, pos, k, n, add, packed, bad);
+    };
+    if (a.nterms == 1) launch(std::integral_constant<int, 1>{});
+    else if (a.nterms == 2) launch(std::integral_constant<int, 2>{});
+    else if (a.nterms == 3) launch(std::integral_constant<int, 3>{});
+    else launch(std::integral_constant<int, 4>{});
+}
+
+void group_launch_bad_total(const uint32_t* bad, uint32_t nbad, unsigned long long* total, hipStream_t st) {
+    hipLaunchKernelGGL(k_group_by_bad, dim3(1), dim3(kTPB), 0, st, bad, nbad, total);
+}
+
+void group_launch_heads(const int32_t* sorted, uint32_t n, uint64_t chunk, uint32_t blocks, uint32_t* ccnt,
+                        unsigned long long* groups, hipStream_t st) {
+    hipLaunchKernelGGL(k_group_heads, dim3(blocks), dim3(kTPB), 0, st, sorted, n, chunk, ccnt, groups);
+}
+
+void group_launch_unpack(const int32_t* codes, uint64_t groups, const int32_t* klo, const uint32_t* krm1, const uint32_t* kstride,
+                         int nkeys, uint32_t flip, int32_t* const* keys_out, uint32_t grid, hipStream_t st) {
+    ByArgs a = {};
+    ByKeysOut o = {};
+    for (int j = 0; j < nkeys; j++) {
+        a.lo[j] = (uint32_t)klo[j];
+        a.rm1[j] = krm1[j];
+        a.stride[j] = kstride[j];
+        o.keys[j] = keys_out[j];
+    }
+    hipLaunchKernelGGL(k_group_by_unpack, dim3(grid), dim3(kTPB), 0, st, codes, (u64)groups, a, nkeys, flip, o);
+}
+
+}  // namespace mqi
 
 extern "C" {
 

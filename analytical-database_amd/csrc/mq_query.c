@@ -1655,6 +1655,168 @@ done:
     return out;
 }
 
+/* The nkeys + 1 + 3 * nmeas Results of a planned measures handle, which is freed here: the key
+ * columns (INT), the counts (LONG), then per measure sums, minima and maxima (LONG each). rc: the
+ * plan's return code. */
+static Result** measures_results(const char* who, mq_mgroup* g, uint64_t groups, int nkeys, int nmeas, int rc, Status* ret_status) {
+    void* buf = NULL;
+    const int nlong = 1 + 3 * nmeas, nres = nkeys + nlong;
+    /* one block: the 8-byte columns first, then the keys */
+    if (!rc) rc = dev_alloc(&buf, groups ? (size_t)groups * (8 * (size_t)nlong + 4 * (size_t)nkeys) : 16);
+    uint64_t* d_count = (uint64_t*)buf;
+    int64_t *d_sum[MQ_GROUP_MAX_MEASURES], *d_min[MQ_GROUP_MAX_MEASURES], *d_max[MQ_GROUP_MAX_MEASURES];
+    for (int m = 0; m < nmeas; m++) {
+        d_sum[m] = (int64_t*)(d_count + groups) + (size_t)(3 * m) * groups;
+        d_min[m] = d_sum[m] + groups;
+        d_max[m] = d_min[m] + groups;
+    }
+    int32_t* d_keys[MQ_GROUP_MAX_KEYS];
+    for (int j = 0; j < nkeys; j++) d_keys[j] = (int32_t*)(d_count + (size_t)nlong * groups) + (size_t)j * groups;
+    if (!rc) rc = mq_group_measures_write(g, d_keys, d_count, d_sum, d_min, d_max, g_stream);
+    mq_group_measures_free(g); /* in g_stream's order, behind the write */
+    if (rc) {
+        mq_stream_sync(g_stream);
+        mq_pool_free(buf);
+        fail(ret_status, who, rc);
+        return NULL;
+    }
+    Result** out = (Result**)calloc((size_t)nres, sizeof(Result*));
+    for (int j = 0; j < nkeys; j++) out[j] = int_result_from_device(d_keys[j], (size_t)groups, ret_status);
+    out[nkeys] = long_result_from_device(d_count, (size_t)groups, ret_status);
+    for (int m = 0; m < nmeas; m++) {
+        out[nkeys + 1 + 3 * m] = long_result_from_device(d_sum[m], (size_t)groups, ret_status);
+        out[nkeys + 2 + 3 * m] = long_result_from_device(d_min[m], (size_t)groups, ret_status);
+        out[nkeys + 3 + 3 * m] = long_result_from_device(d_max[m], (size_t)groups, ret_status);
+    }
+    mq_stream_sync(g_stream);
+    mq_pool_free(buf);
+    for (int i = 0; i < nres; i++)
+        if (!out[i]) {
+            for (int j = 0; j < nres; j++)
+                if (out[j]) {
+                    free(out[j]->payload);
+                    free(out[j]);
+                }
+            free(out);
+            ret_status->code = ERROR;
+            return NULL;
+        }
+    ret_status->code = OK;
+    return out;
+}
+
+/* group_aggregate_star with nmeas measures, each a column or a + b, a - b, a * b of two columns
+ * computed exactly in 64 bits, in place of the value column (no reference counterpart; DESIGN.md
+ * §3.20). Every key map and key set is built per call and freed before returning, on every path. */
+Result** group_aggregate_measures(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn** fkeys,
+                                  GeneralizedColumn** dim_keys, GeneralizedColumn** dim_attrs, int nterms,
+                                  GeneralizedColumn** meas_a, GeneralizedColumn** meas_b, const int* ops, int nmeas,
+                                  Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "group_aggregate_measures";
+    if (nterms < 1 || nterms > MQ_STAR_MAX_TERMS) {
+        dml_fail(ret_status, who, "nterms outside 1..4");
+        return NULL;
+    }
+    if (nmeas < 1 || nmeas > MQ_GROUP_MAX_MEASURES) {
+        dml_fail(ret_status, who, "nmeas outside 1..4");
+        return NULL;
+    }
+    if (!fkeys || !dim_keys || !dim_attrs) {
+        dml_fail(ret_status, who, "fkeys, dim_keys and dim_attrs must each hold nterms entries");
+        return NULL;
+    }
+    if (!meas_a || !ops) {
+        dml_fail(ret_status, who, "meas_a and ops must each hold nmeas entries");
+        return NULL;
+    }
+    for (int m = 0; m < nmeas; m++) {
+        const int binary = ops[m] == MQ_MEAS_ADD || ops[m] == MQ_MEAS_SUB || ops[m] == MQ_MEAS_MUL;
+        const GeneralizedColumn* b = meas_b ? meas_b[m] : NULL;
+        if ((!binary && ops[m] != MQ_MEAS_COL) || (binary && !b) || (!binary && b)) {
+            dml_fail(ret_status, who,
+                     !binary && ops[m] != MQ_MEAS_COL ? "an op outside MQ_MEAS_COL, ADD, SUB, MUL"
+                     : binary                         ? "a binary op needs its meas_b entry"
+                                                      : "MQ_MEAS_COL takes no meas_b entry");
+            return NULL;
+        }
+    }
+    int nkeys = 0;
+    for (int t = 0; t < nterms; t++) {
+        if (!dim_keys[t] && dim_attrs[t]) {
+            dml_fail(ret_status, who, "a term with dim_attrs needs dim_keys");
+            return NULL;
+        }
+        nkeys += !dim_keys[t] || dim_attrs[t];
+    }
+    if (nkeys < 1 || nkeys > MQ_GROUP_MAX_KEYS) {
+        dml_fail(ret_status, who, "the terms must give 1..4 group keys");
+        return NULL;
+    }
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t* dk[MQ_STAR_MAX_TERMS];
+    const int32_t* da[MQ_GROUP_MAX_MEASURES];
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    mq_star_term terms[MQ_STAR_MAX_TERMS] = {{0}};
+    mq_measure meas[MQ_GROUP_MAX_MEASURES] = {{0}};
+    mq_keymap* km[MQ_STAR_MAX_TERMS] = {0};
+    mq_keyset* ks[MQ_STAR_MAX_TERMS] = {0};
+    size_t n = 0;
+    Result** out = NULL;
+    for (int t = 0; t < nterms; t++) { /* the dimensions first: each build synchronises */
+        if (!dim_keys[t]) continue;
+        if (!dim_attrs[t]) {
+            if (in_keyset(who, dim_keys[t], &ks[t], ret_status)) goto done;
+            continue;
+        }
+        const int32_t *ddk = NULL, *dda = NULL;
+        size_t n1 = 0, n1a = 0;
+        const int a = gcol_device(dim_keys[t], &ddk, &n1, ret_status);
+        if (a > 0) goto done;
+        const int b = a < 0 ? a : gcol_device(dim_attrs[t], &dda, &n1a, ret_status);
+        if (b > 0) goto done;
+        if (a < 0 || b < 0 || n1 != n1a || n1 >= ((size_t)1 << 31)) {
+            dml_fail(ret_status, who,
+                     a < 0 || b < 0 ? "dim_keys and dim_attrs must each be a Column or an INT Result"
+                     : n1 != n1a    ? "dim_keys and dim_attrs differ in length"
+                                    : "2^31 dimension rows or more");
+            goto done;
+        }
+        const int rc = mq_keymap_build(ddk, dda, n1, 0, 0, 0, &km[t], NULL, g_stream); /* synchronises */
+        if (rc) {
+            fail(ret_status, who, rc);
+            goto done;
+        }
+    }
+    {
+        int a = by_keys(fkeys, nterms, dk, &n, 0, ret_status);
+        if (!a) a = by_keys(meas_a, nmeas, da, &n, 1, ret_status);
+        for (int m = 0; m < nmeas && !a; m++) {
+            meas[m].d_a = da[m];
+            meas[m].op = ops[m];
+            if (ops[m] != MQ_MEAS_COL) a = by_keys(&meas_b[m], 1, &meas[m].d_b, &n, 1, ret_status);
+        }
+        if (a) {
+            if (a < 0) dml_fail(ret_status, who, a == -1 ? "every fkeys and measure entry must be a Column or an INT Result" : "the fkeys and measures differ in length");
+            goto done;
+        }
+        if (where_args_from(who, 0, 1, columns, lows, highs, ncols, NULL, d_cols, ranges, NULL, &n, ret_status)) goto done;
+        for (int t = 0; t < nterms; t++) terms[t] = (mq_star_term){dk[t], km[t], ks[t]};
+        mq_mgroup* g = NULL;
+        uint64_t groups = 0;
+        const int rc = mq_group_measures_plan(d_cols, ranges, ncols, terms, nterms, meas, nmeas, n, NULL, MQ_GROUP_AUTO, &g, &groups,
+                                              NULL, NULL, g_stream);
+        out = measures_results(who, g, groups, nkeys, nmeas, rc, ret_status);
+    }
+done:
+    mq_stream_sync(g_stream);
+    for (int t = 0; t < nterms; t++) {
+        mq_keymap_free(km[t]);
+        mq_keyset_free(ks[t]);
+    }
+    return out;
+}
+
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner
  * ascending — exactly a hash join that builds on the inner side (insertion
  * order = inner order) and probes with the outer side, outputs swapped. */

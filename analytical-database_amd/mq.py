@@ -30,6 +30,8 @@ MQ_TOPK_SORT_DIV = 4
 MQ_WHERE_MAX_COLS = 8
 MQ_SEMI_AUTO, MQ_SEMI_LDS, MQ_SEMI_GLOBAL = 0, 1, 2
 MQ_STAR_MAX_TERMS = 4
+MQ_GROUP_MAX_MEASURES = 4
+MQ_MEAS_COL, MQ_MEAS_ADD, MQ_MEAS_SUB, MQ_MEAS_MUL = 0, 1, 2, 3
 MQ_JOIN_STATE_WORDS = 3  # include/mq_device.h mq_join_state
 (MQ_JOIN_STATE_PART, MQ_JOIN_STATE_DUPW, MQ_JOIN_STATE_PACKED, MQ_JOIN_STATE_RS, MQ_JOIN_STATE_PRUNS,
  MQ_JOIN_STATE_RUN2, MQ_JOIN_STATE_DEFERRED, MQ_JOIN_STATE_ROW_WRITE) = (1 << b for b in range(8))
@@ -60,6 +62,10 @@ class MqKeymapInfo(C.Structure):  # include/mq_device.h mq_keymap_info
 
 class MqStarTerm(C.Structure):  # include/mq_device.h mq_star_term
     _fields_ = [("d_col", C.c_void_p), ("km", C.c_void_p), ("ks", C.c_void_p)]
+
+
+class MqMeasure(C.Structure):  # include/mq_device.h mq_measure
+    _fields_ = [("d_a", C.c_void_p), ("d_b", C.c_void_p), ("op", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ColumnIndex(C.Structure):
@@ -248,6 +254,13 @@ _SIGS = {
                                  _sz, _vp]),
     "mq_group_star_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, C.POINTER(MqStarTerm), _int, _vp, _u64, _vp, _int,
                                   C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_int), C.POINTER(_u64), _vp]),
+    "mq_group_measures_dense_slots": (C.c_uint32, [_int]),
+    "mq_group_measures_auto_path": (_int, [C.POINTER(_i32), _int, _int, C.POINTER(_u64)]),
+    "mq_group_measures_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, C.POINTER(MqStarTerm), _int, C.POINTER(MqMeasure),
+                                      _int, _u64, _vp, _int, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_int), C.POINTER(_u64),
+                                      _vp]),
+    "mq_group_measures_write": (_int, [_vp, C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "mq_group_measures_free": (_int, [_vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -313,6 +326,11 @@ _SIGS = {
                                               C.POINTER(C.POINTER(_int)), _int, C.POINTER(C.POINTER(GeneralizedColumn)),
                                               C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(GeneralizedColumn)),
                                               _int, C.POINTER(GeneralizedColumn), _PS]),
+    "group_aggregate_measures": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                                                  C.POINTER(C.POINTER(_int)), _int, C.POINTER(C.POINTER(GeneralizedColumn)),
+                                                  C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(GeneralizedColumn)),
+                                                  _int, C.POINTER(C.POINTER(GeneralizedColumn)),
+                                                  C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(_int), _int, _PS]),
     "group_aggregate_by": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), _int, C.POINTER(GeneralizedColumn),
                                             _PS]),
     "group_aggregate_by_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),

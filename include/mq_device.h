@@ -856,6 +856,74 @@ int mq_group_star_plan(const int32_t* const* d_cols, const mq_range* h_ranges, i
                        const int32_t* h_key_bounds /* NULL or 2*nkeys host ints */, int path,
                        mq_group** out, uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream);
 
+/* ---- Several expression aggregates over a star query's groups, in one pass ----
+ *   SELECT d1.a, f.k, count(*), sum(f.x), min(f.x), max(f.x), sum(f.x * f.y), .., sum(f.x - f.z), ..
+ *   FROM f JOIN d1 .. WHERE .. GROUP BY d1.a, f.k
+ * The joined rows, the tuples, their order, the bounds rules, *h_rows and the shapes settled on the
+ * host (n == 0, an unsatisfiable range, an empty map or set) are exactly mq_group_star_plan's with
+ * the same ranges, terms and bounds. In place of one value column there are nmeas measures
+ * (1..MQ_GROUP_MAX_MEASURES), each a column or a binary expression of two columns (mq_measure).
+ * value: for row i, computed EXACTLY in int64 from the int32 operands: a, a + b, a - b or a * b
+ *        (|a * b| <= 2^62: all four fit). This is not mq_add / mq_sub's int32 wrap:
+ *        INT32_MIN - INT32_MAX is -4294967295.
+ * outputs: per group one uint64_t count and, per measure, an int64_t sum, min and max over the
+ *        group's joined rows. The sum is taken modulo 2^64 (two's complement; accumulated in
+ *        unsigned 64-bit everywhere, so no signed overflow is evaluated) and is therefore bitwise
+ *        independent of the order of addition, the path, the grid and the alignment.
+ * aliasing: any operand may be the same column as the other operand, a term's or a predicate's.
+ * reads: the host collects the DISTINCT operand pointers (at most 8); the dense kernel loads each
+ *        once per tile, and of each only the 128-byte lines that still hold a joined row. A
+ *        dropped row's operands never reach an aggregate.
+ * dense: a slot costs 4 + 24 * nmeas bytes of LDS (u32 count; u64 sum, i64 min, i64 max per
+ *        measure). mq_group_measures_dense_slots(nmeas) is the largest power of two whose table
+ *        fits the 40 KiB of every dense grouping kernel: 1024, 512, 512, 256 for nmeas 1..4 (0 for
+ *        any other nmeas). P = prod(hi_j - lo_j + 1) <= that capacity takes the dense path under
+ *        MQ_GROUP_AUTO; MQ_GROUP_DENSE forced past it, or P > 2^32, is MQ_EINVAL.
+ *        mq_group_measures_auto_path answers from bounds alone, as mq_group_by_auto_path does.
+ *        mq_group_dense_slots() and the single-value plans are unchanged.
+ *        k_group_measures_dense: k_group_star_dense's front half, then the operand lines, the
+ *        measures (op is uniform over the grid) and LDS atomics (one on the count and a 64-bit add,
+ *        min and max per measure), with the wave-uniform run fold; k_measures_fold,
+ *        k_measures_rank and k_measures_dense_write serve the wider slot.
+ * sort:  mq_star_positions gives the K joined rows, k_group_star_pack_pos their codes,
+ *        k_measures_eval_pos one int64 column of K values per measure; mq_index_build sorts the
+ *        codes and k_measures_seg_write folds the values through the sorted positions. The handle
+ *        owns every buffer and frees them in the order of the stream of the last write.
+ * contract: the plan SYNCHRONISES. The write is asynchronous on `stream`, may be repeated (on any
+ *        stream of the device), takes NULL for d_keys_out, d_count_out, d_sum_out, d_min_out,
+ *        d_max_out or for any entry of the host arrays (nkeys resp. nmeas device pointers), and
+ *        writes nothing at or past entry *h_groups. The measure columns must stay valid until the
+ *        last write has completed.
+ * MQ_EINVAL with *out = NULL, *h_groups = 0, *h_rows = 0 and nothing allocated: everything
+ * mq_group_star_plan refuses; nmeas outside 1..4; a NULL h_meas; an op outside the four; with
+ * n > 0 a NULL or not 4-byte aligned d_a (or misaligned d_b); d_b NULL for a binary op or non-NULL
+ * for MQ_MEAS_COL; reserved != 0. A joined row with a component out of its bounds is MQ_EINVAL with
+ * everything released, and is never used as an address.
+ * Not measured on a device yet (tools/bench_measures.py is the sweep). */
+enum { MQ_GROUP_MAX_MEASURES = 4 };
+enum { MQ_MEAS_COL = 0, MQ_MEAS_ADD = 1, MQ_MEAS_SUB = 2, MQ_MEAS_MUL = 3 };
+typedef struct mq_measure {            /* 24 bytes */
+    const int32_t* d_a;                /* n rows */
+    const int32_t* d_b;                /* n rows; must be NULL for MQ_MEAS_COL */
+    int32_t op, reserved;              /* MQ_MEAS_*; reserved must be 0 */
+} mq_measure;
+typedef struct mq_mgroup mq_mgroup;
+uint32_t mq_group_measures_dense_slots(int nmeas);      /* needs no device; 0 for nmeas outside 1..4 */
+/* needs no device: MQ_GROUP_DENSE or MQ_GROUP_SORT for the bounds' key space (*h_space, may be NULL);
+ * MQ_EINVAL for empty bounds, a space past 2^32, nkeys or nmeas outside 1..4 */
+int mq_group_measures_auto_path(const int32_t* h_key_bounds, int nkeys, int nmeas, uint64_t* h_space);
+int mq_group_measures_plan(const int32_t* const* d_cols, const mq_range* h_ranges, int ncols /* 0..8 */,
+                           const mq_star_term* h_terms, int nterms /* 1..4 */,
+                           const mq_measure* h_meas, int nmeas /* 1..4 */, uint64_t n,
+                           const int32_t* h_key_bounds /* NULL or 2*nkeys host ints */, int path,
+                           mq_mgroup** out, uint64_t* h_groups, int* h_path, uint64_t* h_rows, void* stream);
+int mq_group_measures_write(mq_mgroup* g, int32_t* const* d_keys_out /* NULL or nkeys ptrs, any NULL */,
+                            uint64_t* d_count_out,
+                            int64_t* const* d_sum_out, int64_t* const* d_min_out, int64_t* const* d_max_out
+                            /* each NULL or a host array of nmeas device pointers, any of them NULL */,
+                            void* stream);
+int mq_group_measures_free(mq_mgroup* g);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

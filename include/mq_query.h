@@ -470,6 +470,24 @@ Result** group_aggregate_star(GeneralizedColumn** columns, int** lows, int** hig
                               GeneralizedColumn** dim_attrs, int nterms /* 1..4 */,
                               GeneralizedColumn* values, Status* ret_status);
 
+/* ---- Several expression aggregates over a star query's groups (not in the reference) ----
+ * group_aggregate_measures: group_aggregate_star with nmeas (1..4) measures in place of `values`
+ * (mq_group_measures_plan in mq_device.h). Measure m is meas_a[m] (ops[m] ==
+ * MQ_MEAS_COL, and meas_b[m] must be NULL, as may meas_b itself when no measure is binary) or
+ * meas_a[m] + / - / * meas_b[m] (MQ_MEAS_ADD / MQ_MEAS_SUB / MQ_MEAS_MUL), computed exactly in 64
+ * bits per row. Every operand is a COLUMN or an INT RESULT as long as the columns; operands may
+ * repeat and may be term or predicate columns. The other arguments and the ownership, shadow and
+ * error rules are group_aggregate_star's. Returns nkeys + 1 + 3 * nmeas Results: the key columns
+ * (INT), the counts (LONG), then per measure its sums (modulo 2^64), minima and maxima (LONG
+ * each), one tuple per distinct key tuple with a joined row, ascending lexicographically. ERROR
+ * and NULL also for nmeas outside 1..4, an op outside the four, a missing or a superfluous
+ * meas_b[m]. Not measured on a device yet. */
+Result** group_aggregate_measures(GeneralizedColumn** columns, int** lows, int** highs, int ncols /* 0..8 */,
+                                  GeneralizedColumn** fkeys, GeneralizedColumn** dim_keys,
+                                  GeneralizedColumn** dim_attrs, int nterms /* 1..4 */,
+                                  GeneralizedColumn** meas_a, GeneralizedColumn** meas_b /* entries NULL for COL */,
+                                  const int* ops, int nmeas /* 1..4 */, Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
