@@ -3026,6 +3026,99 @@ int mq_group_by_write(mq_group* g, int32_t* const* d_keys_out, uint64_t* d_count
     return rc;
 }
 
+// HAVING, ORDER BY an aggregate and LIMIT over the handle's groups: the handle's
+// own write into pool buffers, mq_topk64 on the ordering and filter aggregates as int64 columns,
+// the requested outputs gathered through its indices. The kernels are mq_topk64.hip's.
+int mq_group_top(mq_group* g, const mq_group_order* o, uint64_t* h_m, int32_t* const* d_keys_out, uint64_t* d_count_out,
+                 int64_t* d_sum_out, int32_t* d_min_out, int32_t* d_max_out, mq_topk64_info* h_info, void* stream) {
+    DevState* s;
+    int rc = ensure_ready(&s);
+    if (rc) return rc;
+    if (h_info) *h_info = mq_topk64_info{};
+    if (h_m) *h_m = 0;
+    if (!g || !o || !h_m) return set_err(MQ_EINVAL, "mq_group_top: NULL pointer");
+    if (o->order_by < MQ_AGG_KEY || o->order_by > MQ_AGG_MAX) return set_err(MQ_EINVAL, "mq_group_top: order_by %d", o->order_by);
+    if (o->having_by < MQ_AGG_KEY || o->having_by > MQ_AGG_MAX) return set_err(MQ_EINVAL, "mq_group_top: having_by %d", o->having_by);
+    if (o->path != MQ_TOPK_AUTO && o->path != MQ_TOPK_SELECT && o->path != MQ_TOPK_SORT)
+        return set_err(MQ_EINVAL, "mq_group_top: path %d", o->path);
+    int dev = -1;
+    if ((rc = current_device(&dev))) return rc;
+    if (dev != g->dev) return set_err(MQ_EINVAL, "mq_group_top: the plan was made on device %d", g->dev);
+    if (g->groups == 0) return MQ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    g->stream = st;
+    const uint64_t G = g->groups;
+    const int nkeys = g->nkeys > 1 ? g->nkeys : 1;
+    const uint64_t cap = o->k < G ? o->k : G;
+
+    struct Bufs {  // the call's pool buffers: freed once the stream has drained, on every way out
+        void* p[kMaxKeys + 8];
+        int used = 0;
+        hipStream_t st;
+        void* get(size_t bytes) {
+            void* q = pool_alloc(bytes ? bytes : 16);
+            if (q) p[used++] = q;
+            return q;
+        }
+        ~Bufs() {
+            if (used) (void)hipStreamSynchronize(st);
+            for (int i = 0; i < used; i++) pool_free(p[i]);
+        }
+    } bufs;
+    bufs.st = st;
+
+    // every group's aggregates that order, filter or leave, as the handle writes them
+    void* const outs[5] = {nullptr, d_count_out, d_sum_out, d_min_out, d_max_out};
+    void* full[5] = {};
+    bool ok = true;
+    for (int a = MQ_AGG_COUNT; a <= MQ_AGG_MAX; a++)
+        if (outs[a] || o->order_by == a || o->having_by == a)
+            ok = ok && (full[a] = bufs.get(G * (a <= MQ_AGG_SUM ? 8 : 4)));
+    int32_t* kfull[kMaxKeys] = {};
+    for (int j = 0; j < nkeys; j++)
+        if (d_keys_out && d_keys_out[j]) ok = ok && (kfull[j] = static_cast<int32_t*>(bufs.get(G * 4)));
+    uint32_t* idx = static_cast<uint32_t*>(bufs.get(cap * 4));
+    if (!ok || !idx) return set_err(MQ_ENOMEM, "mq_group_top: allocation failed");
+    rc = mq_group_by_write(g, kfull, static_cast<uint64_t*>(full[MQ_AGG_COUNT]), static_cast<int64_t*>(full[MQ_AGG_SUM]),
+                           static_cast<int32_t*>(full[MQ_AGG_MIN]), static_cast<int32_t*>(full[MQ_AGG_MAX]), stream);
+    if (rc) return rc;
+    // the ordering and the filter aggregate as int64 columns: a count (below 2^31) and a sum are
+    // one already, a min or max is widened
+    const uint32_t grid = stream_grid(s, G);
+    int64_t* wide[5] = {};
+    auto as64 = [&](int a) -> const int64_t* {
+        if (a == MQ_AGG_KEY) return nullptr;
+        if (a <= MQ_AGG_SUM) return static_cast<const int64_t*>(full[a]);
+        if (!wide[a] && (wide[a] = static_cast<int64_t*>(bufs.get(G * 8))))
+            topk64_launch_widen(static_cast<const int32_t*>(full[a]), G, wide[a], grid, st);
+        return wide[a];
+    };
+    const int64_t* ord = as64(o->order_by);
+    const int64_t* hav = as64(o->having_by);
+    if ((o->order_by != MQ_AGG_KEY && !ord) || (o->having_by != MQ_AGG_KEY && !hav))
+        return set_err(MQ_ENOMEM, "mq_group_top: allocation failed");
+    LAUNCHCHK("k_topk64_widen");
+    mq_topk64_info info;
+    rc = mq_topk64(ord, hav, &o->having, G, o->k, o->descending, o->path, o->cand_cap, nullptr, idx, &info, stream);
+    if (rc) return rc;
+    const uint64_t m = info.m;
+    if (m) {
+        const uint32_t gm = stream_grid(s, m);
+        for (int j = 0; j < nkeys; j++)
+            if (kfull[j]) topk64_launch_take32(kfull[j], idx, m, d_keys_out[j], gm, st);
+        for (int a = MQ_AGG_COUNT; a <= MQ_AGG_MAX; a++) {
+            if (!outs[a]) continue;
+            if (a <= MQ_AGG_SUM) topk64_launch_take64(static_cast<const int64_t*>(full[a]), idx, m, static_cast<int64_t*>(outs[a]), gm, st);
+            else topk64_launch_take32(static_cast<const int32_t*>(full[a]), idx, m, static_cast<int32_t*>(outs[a]), gm, st);
+        }
+        LAUNCHCHK("k_topk64_take");
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (h_info) *h_info = info;
+    *h_m = m;
+    return MQ_OK;
+}
+
 int mq_group_free(mq_group* g) {
     DevState* s;
     int rc = ensure_ready(&s);

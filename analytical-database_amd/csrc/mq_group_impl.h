@@ -28,4 +28,11 @@ void group_launch_heads(const int32_t* sorted, uint32_t n, uint64_t chunk, uint3
 void group_launch_unpack(const int32_t* codes, uint64_t groups, const int32_t* klo, const uint32_t* krm1, const uint32_t* kstride,
                          int nkeys, uint32_t flip, int32_t* const* keys_out, uint32_t grid, hipStream_t st);
 
+// What mq_topk64.hip lends mq_group_top, on `grid` blocks of a grid-stride loop each:
+// k_topk64_widen: out[i] = in[i] sign-extended, i < n.
+void topk64_launch_widen(const int32_t* in, uint64_t n, int64_t* out, uint32_t grid, hipStream_t st);
+// k_topk64_take: out[i] = col[idx[i]], i < m.
+void topk64_launch_take32(const int32_t* col, const uint32_t* idx, uint64_t m, int32_t* out, uint32_t grid, hipStream_t st);
+void topk64_launch_take64(const int64_t* col, const uint32_t* idx, uint64_t m, int64_t* out, uint32_t grid, hipStream_t st);
+
 }  // namespace mqi

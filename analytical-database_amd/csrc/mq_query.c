@@ -1817,6 +1817,121 @@ done:
     return out;
 }
 
+/* HAVING, ORDER BY an aggregate and LIMIT over the Results of any group_aggregate* (no reference
+ * counterpart): the tuples for which low <= groups[having_by] < high holds, the
+ * first k of them in a stable sort by groups[order_by], every Result gathered through the order.
+ * INT inputs are read through their shadows, LONG ones are uploaded; mq_topk64 orders on the
+ * device and mq_topk64_take gathers. */
+Result** group_top_k(Result** groups, int nresults, int order_by, bool descending, size_t k, int having_by, const long* low,
+                     const long* high, Status* ret_status) {
+    const char* who = "group_top_k";
+    if (op_begin(ret_status)) return NULL;
+    const char* bad = NULL;
+    if (!groups || nresults < 1) bad = "no Results";
+    else if (order_by < -1 || order_by >= nresults || having_by < -1 || having_by >= nresults) bad = "an index outside the Results";
+    for (int i = 0; !bad && i < nresults; i++) {
+        const Result* r = groups[i];
+        if (!r || (r->data_type != INT && r->data_type != LONG) || (r->num_tuples && !r->payload)) bad = "every Result must be INT or LONG";
+        else if (r->num_tuples != groups[0]->num_tuples) bad = "the Results differ in length";
+    }
+    if (!bad && groups[0]->num_tuples >= ((size_t)1 << 31)) bad = "2^31 tuples or more";
+    if (bad) {
+        dml_fail(ret_status, who, bad);
+        return NULL;
+    }
+    const size_t n = groups[0]->num_tuples;
+    const void** d_in = (const void**)calloc((size_t)nresults, sizeof(void*));
+    void** owned = (void**)calloc((size_t)nresults + 4, sizeof(void*)); /* what this call allocated on the device */
+    Result** out = (Result**)calloc((size_t)nresults, sizeof(Result*));
+    int nowned = 0, rc = 0, failed = 0;
+    uint64_t m = 0;
+    void* d_out = NULL;
+    if (n && k) {
+        for (int i = 0; i < nresults && !failed; i++) {
+            const Result* r = groups[i];
+            if (r->data_type == INT) {
+                const int32_t* d = NULL;
+                failed = result_device(r, &d, ret_status) != 0;
+                d_in[i] = d;
+            } else {
+                void* d = NULL;
+                if ((rc = dev_alloc(&d, n * sizeof(long))) || (owned[nowned++] = d, rc = h2d(d, r->payload, n * sizeof(long)))) {
+                    fail(ret_status, "result upload", rc);
+                    failed = 1;
+                }
+                d_in[i] = d;
+            }
+        }
+        /* the ordering and the filter column as int64 */
+        const int64_t* d64[2] = {NULL, NULL};
+        const int which[2] = {order_by, having_by};
+        for (int j = 0; j < 2 && !failed; j++) {
+            const int i = which[j];
+            if (i < 0) continue;
+            if (j == 1 && i == which[0]) d64[1] = d64[0];
+            else if (groups[i]->data_type == LONG) d64[j] = (const int64_t*)d_in[i];
+            else {
+                void* w = NULL;
+                if ((rc = dev_alloc(&w, n * 8)) || (owned[nowned++] = w, rc = mq_topk64_widen((const int32_t*)d_in[i], n, (int64_t*)w, g_stream))) {
+                    fail(ret_status, who, rc);
+                    failed = 1;
+                }
+                d64[j] = (const int64_t*)w;
+            }
+        }
+        const size_t cap = k < n ? k : n;
+        void* d_idx = NULL;
+        if (!failed && ((rc = dev_alloc(&d_idx, cap * 4)) || (owned[nowned++] = d_idx, rc = dev_alloc(&d_out, cap * 8)))) {
+            fail(ret_status, who, rc);
+            failed = 1;
+        }
+        if (!failed) {
+            const mq_range64 range = {low != NULL, low ? *low : 0, high != NULL, high ? *high : 0};
+            mq_topk64_info info = {0};
+            rc = mq_topk64(d64[0], d64[1], &range, n, k, descending, MQ_TOPK_AUTO, 0, NULL, (uint32_t*)d_idx, &info, g_stream);
+            if (rc) {
+                fail(ret_status, who, rc);
+                failed = 1;
+            }
+            m = info.m;
+        }
+        /* one staging buffer serves every Result in turn: each download drains the stream */
+        for (int i = 0; i < nresults && !failed; i++) {
+            const int is_int = groups[i]->data_type == INT;
+            if ((rc = mq_topk64_take(d_in[i], is_int ? 4 : 8, (const uint32_t*)d_idx, m, d_out, g_stream))) {
+                fail(ret_status, who, rc);
+                failed = 1;
+                break;
+            }
+            out[i] = is_int ? int_result_from_device(d_out, (size_t)m, ret_status) : long_result_from_device(d_out, (size_t)m, ret_status);
+            if (!out[i]) failed = 1;
+            mq_stream_sync(g_stream); /* a shadow's copy out of d_out is queued behind the download */
+        }
+    } else {
+        for (int i = 0; i < nresults && !failed; i++) {
+            out[i] = groups[i]->data_type == INT ? int_result_from_device(NULL, 0, ret_status) : long_result_from_device(NULL, 0, ret_status);
+            if (!out[i]) failed = 1;
+        }
+    }
+    mq_stream_sync(g_stream);
+    mq_pool_free(d_out);
+    for (int i = 0; i < nowned; i++) mq_pool_free(owned[i]);
+    free(owned);
+    free((void*)d_in);
+    if (failed) {
+        for (int i = 0; i < nresults; i++)
+            if (out[i]) {
+                free(out[i]->payload);
+                free(out[i]);
+            }
+        free(out);
+        ret_status->code = ERROR;
+        return NULL;
+    }
+    ret_status->code = OK;
+    return out;
+}
+
 /* query.c:585-650: outer column_one x inner column_two, outer-major with inner
  * ascending — exactly a hash join that builds on the inner side (insertion
  * order = inner order) and probes with the outer side, outputs swapped. */

@@ -27,6 +27,7 @@ MQ_GROUP_AUTO, MQ_GROUP_DENSE, MQ_GROUP_SORT = 0, 1, 2
 MQ_GROUP_MAX_KEYS = 4
 MQ_TOPK_AUTO, MQ_TOPK_SELECT, MQ_TOPK_SORT = 0, 1, 2
 MQ_TOPK_SORT_DIV = 4
+MQ_AGG_KEY, MQ_AGG_COUNT, MQ_AGG_SUM, MQ_AGG_MIN, MQ_AGG_MAX = 0, 1, 2, 3, 4
 MQ_WHERE_MAX_COLS = 8
 MQ_SEMI_AUTO, MQ_SEMI_LDS, MQ_SEMI_GLOBAL = 0, 1, 2
 MQ_STAR_MAX_TERMS = 4
@@ -45,6 +46,20 @@ class MqAgg(C.Structure):
 class MqTopkInfo(C.Structure):  # include/mq_device.h mq_topk_info
     _fields_ = [("m", C.c_uint64), ("candidates", C.c_uint64), ("ties", C.c_uint64),
                 ("path", C.c_int32), ("levels", C.c_int32)]
+
+
+class MqRange64(C.Structure):  # include/mq_device.h mq_range64
+    _fields_ = [("has_low", C.c_int), ("low", C.c_int64), ("has_high", C.c_int), ("high", C.c_int64)]
+
+
+class MqTopk64Info(C.Structure):  # include/mq_device.h mq_topk64_info
+    _fields_ = [("m", C.c_uint64), ("passed", C.c_uint64), ("candidates", C.c_uint64), ("ties", C.c_uint64),
+                ("path", C.c_int32), ("levels", C.c_int32)]
+
+
+class MqGroupOrder(C.Structure):  # include/mq_device.h mq_group_order
+    _fields_ = [("order_by", C.c_int), ("descending", C.c_int), ("k", C.c_uint64), ("having_by", C.c_int),
+                ("having", MqRange64), ("path", C.c_int), ("cand_cap", C.c_uint64)]
 
 
 class MqRange(C.Structure):  # include/mq_device.h mq_range
@@ -232,6 +247,13 @@ _SIGS = {
     "mq_topk_default_cap": (_u64, []),
     "mq_topk_auto_path": (_int, [_u64, _u64, _u64]),
     "mq_topk": (_int, [_vp, _vp, _u64, _u64, _int, _int, _u64, _vp, _vp, C.POINTER(MqTopkInfo), _vp]),
+    "mq_topk64_key": (_u64, [C.c_int64, _int]),
+    "mq_topk64_auto_path": (_int, [_u64, _u64, _u64]),
+    "mq_topk64": (_int, [_vp, _vp, C.POINTER(MqRange64), _u64, _u64, _int, _int, _u64, _vp, _vp, C.POINTER(MqTopk64Info), _vp]),
+    "mq_topk64_widen": (_int, [_vp, _u64, _vp, _vp]),
+    "mq_topk64_take": (_int, [_vp, _int, _vp, _u64, _vp, _vp]),
+    "mq_group_top": (_int, [_vp, C.POINTER(MqGroupOrder), C.POINTER(_u64), C.POINTER(_vp), _vp, _vp, _vp, _vp,
+                            C.POINTER(MqTopk64Info), _vp]),
     "mq_where_workspace_bytes": (_sz, [_u64]),
     "mq_where_positions": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _u64, _vp, _vp, _vp, _sz, _vp]),
     "mq_where_agg": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, _vp, _u64, _vp, _vp, _sz, _vp]),
@@ -305,6 +327,8 @@ _SIGS = {
     "hash_join": (C.POINTER(_PR), [_PR, _PR, _PR, _PR, _PS]),
     "group_aggregate": (C.POINTER(_PR), [C.POINTER(GeneralizedColumn), C.POINTER(GeneralizedColumn), _PS]),
     "top_k": (C.POINTER(_PR), [C.POINTER(GeneralizedColumn), _PR, _sz, C.c_bool, _PS]),
+    "group_top_k": (C.POINTER(_PR), [C.POINTER(_PR), _int, _int, C.c_bool, _sz, _int, C.POINTER(C.c_long), C.POINTER(C.c_long),
+                                     _PS]),
     "select_where": (_PR, [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
                            C.POINTER(C.POINTER(_int)), _int, _PR, _PS]),
     "aggregate_where": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),

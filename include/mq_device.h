@@ -608,6 +608,95 @@ int mq_topk(const int32_t* d_vals, const int32_t* d_payload /* may be NULL */, u
             int32_t* d_vals_out, int32_t* d_payload_out, mq_topk_info* h_info /* may be NULL */,
             void* stream);
 
+/* ---- HAVING, ORDER BY an aggregate and LIMIT: top k over int64 entries ----
+ * n < 2^31 entries. Entry i passes when d_having is NULL or h_having (low <= v < high, either
+ * bound optional) holds for d_having[i]. The output is the first m = min(k, passed) passing
+ * entries of a stable sort by d_vals[i], as pairs (value, index i): ascending, the smallest
+ * first; descending (descending != 0), the largest first, that is a stable sort by ~v; equal
+ * values in ascending i in both directions (numpy: idx = flatnonzero(mask);
+ * idx[argsort(v[idx], kind="stable")][:k], of ~v[idx] for descending). With d_vals == NULL the
+ * order is i itself, whatever `descending` says: an ordered compaction of the passing entries
+ * cut at k (HAVING alone, in key order), and d_vals_out receives the index as an int64; both
+ * paths are then one counting read and the collect (candidates = m, ties = 0, levels = 1 on
+ * the select path).
+ * d_having may equal d_vals. The result is unique, so it is bitwise the same on every path,
+ * grid and cand_cap. The reference has no such operator.
+ * select: §3.12's radix select on 64-bit keys. Each value maps to a u64 in output order (sign bit
+ *        flipped, complemented for descending; mq_topk64_key). One streaming read, 16-byte loads,
+ *        counts the passing entries' top 11 key bits into 2048 LDS bins a block; with a filter
+ *        column of its own the value is requested only for a wave tile (256 entries) in which an
+ *        entry passed. While the boundary bin holds more than cand_cap entries the read repeats
+ *        over that prefix alone for the next digit (shifts 53, 42, 31, 20, 9, 0, the last digit 9
+ *        bits: at most six reads, h_info->levels). One ordered collect read takes every passing
+ *        entry before the boundary prefix and the entries on it: all of them when they fit
+ *        cand_cap, else (the prefix is one value by then) the first m - (entries before). The
+ *        candidates, at most k + cand_cap, are sorted by (key, index) with two stable
+ *        mq_index_build runs (low word, then high word) and the first m gathered. Workspace
+ *        O(k + cand_cap + blocks), from the pool.
+ * sort:  one counting read, the passing entries compacted and all of them sorted the same way:
+ *        ORDER BY without a LIMIT is k = UINT64_MAX.
+ * MQ_TOPK_AUTO is mq_topk's rule with mq_topk's constants (mq_topk64_auto_path; needs no device):
+ * sort when min(k, n) + cand_cap > n / MQ_TOPK_SORT_DIV. The constants have NOT been swept for
+ * 64-bit entries. cand_cap == 0 means mq_topk_default_cap().
+ * Synchronises, as mq_topk does. Either output may be NULL; nothing is written at or past entry
+ * m. k == 0 or n == 0 gives m = 0 and MQ_OK. MQ_EINVAL, with nothing written: n >= 2^31, a
+ * d_vals, d_having or d_vals_out that is not 8-byte aligned, a d_idx_out that is not 4-byte
+ * aligned, d_having set with h_having NULL, a path that is none of the three.
+ * mq_topk64_widen (d_out[i] = d_in[i], sign-extended) and mq_topk64_take (d_out[i] =
+ * d_col[d_idx[i]], elements of 4 or 8 bytes) are the asynchronous helpers around it: a column of
+ * int32 aggregates made sortable, and any column gathered through the indices. */
+typedef struct mq_range64 { int has_low; int64_t low; int has_high; int64_t high; } mq_range64; /* low <= v < high */
+typedef struct mq_topk64_info {
+    uint64_t m;          /* entries written: min(k, passed) */
+    uint64_t passed;     /* entries for which the filter holds (n without a filter) */
+    uint64_t candidates; /* entries handed to the final sort (sort path: passed) */
+    uint64_t ties;       /* passing entries equal to entry m-1's value that were left out */
+    int32_t  path;       /* MQ_TOPK_SELECT or MQ_TOPK_SORT */
+    int32_t  levels;     /* histogram reads (select path 1..6, sort path 0) */
+} mq_topk64_info;
+uint64_t mq_topk64_key(int64_t v, int descending);   /* host-callable; needs no device */
+int mq_topk64_auto_path(uint64_t n, uint64_t k, uint64_t cand_cap /* 0: mq_topk_default_cap() */);
+int mq_topk64(const int64_t* d_vals /* NULL: order by the entry's index */,
+              const int64_t* d_having /* NULL: no filter */, const mq_range64* h_having,
+              uint64_t n, uint64_t k, int descending, int path, uint64_t cand_cap,
+              int64_t* d_vals_out /* may be NULL */, uint32_t* d_idx_out /* may be NULL */,
+              mq_topk64_info* h_info /* may be NULL */, void* stream);
+int mq_topk64_widen(const int32_t* d_in, uint64_t n, int64_t* d_out, void* stream);
+int mq_topk64_take(const void* d_col, int elem_bytes /* 4 or 8 */, const uint32_t* d_idx, uint64_t m,
+                   void* d_out, void* stream);
+
+/* ---- the same on a group handle: HAVING, ORDER BY, LIMIT over its groups ----
+ * g is an mq_group from mq_group_plan, _where_, _by_, _by_where_, _join_ or _star_plan. The
+ * entries are its groups in key order (the order mq_group_write / mq_group_by_write give,
+ * lexicographic tuples). The ordering aggregate o->order_by and the filter aggregate
+ * o->having_by are materialised as int64 columns of `groups` entries (the handle's own write
+ * into pool buffers; int32 min / max widened), mq_topk64 runs on them and every requested output
+ * is gathered through its indices: ties in the ordering aggregate come in ascending key order, and
+ * the result equals mq_group_by_write of everything followed by the numpy model above.
+ * order_by == MQ_AGG_KEY keeps key order (HAVING and LIMIT only; `descending` is ignored);
+ * having_by == MQ_AGG_KEY (0) means no HAVING. Output capacity min(k, groups) each; *h_m = the
+ * entries written. d_keys_out is NULL or a host array of the handle's nkeys (>= 1) device
+ * pointers, any of them NULL. The handle stays usable: mq_group_write still gives all groups,
+ * and mq_group_top may be repeated with another order. Synchronises (mq_topk64 does). The device
+ * check, the stream bookkeeping and groups == 0 (*h_m = 0, MQ_OK) are mq_group_write's.
+ * MQ_EINVAL: an order_by or having_by that is no MQ_AGG_*, a NULL g, o or h_m, and mq_topk64's
+ * own cases. mq_mgroup handles (mq_group_measures_plan) have no such form: their results go
+ * through the drop-in group_top_k (mq_query.h). */
+enum { MQ_AGG_KEY = 0, MQ_AGG_COUNT = 1, MQ_AGG_SUM = 2, MQ_AGG_MIN = 3, MQ_AGG_MAX = 4 };
+typedef struct mq_group_order {
+    int order_by;      /* MQ_AGG_*; MQ_AGG_KEY: key order, i.e. HAVING and LIMIT only */
+    int descending;
+    uint64_t k;        /* UINT64_MAX: no LIMIT */
+    int having_by;     /* MQ_AGG_COUNT..MQ_AGG_MAX, or MQ_AGG_KEY (0): no HAVING */
+    mq_range64 having;
+    int path;          /* MQ_TOPK_* */
+    uint64_t cand_cap; /* 0: default */
+} mq_group_order;
+int mq_group_top(mq_group* g, const mq_group_order* o, uint64_t* h_m,
+                 int32_t* const* d_keys_out /* NULL, or host array of the handle's nkeys (>= 1) pointers, any NULL */,
+                 uint64_t* d_count_out, int64_t* d_sum_out, int32_t* d_min_out, int32_t* d_max_out,
+                 mq_topk64_info* h_info, void* stream);
+
 /* ---- WHERE a IN [..) AND b IN [..) ...: a conjunctive range select ----
  * ncols (1 .. MQ_WHERE_MAX_COLS) columns of n < 2^31 int32 rows and one range per column:
  * row i matches when every range holds for it. A range is {has_low, low, has_high, high}

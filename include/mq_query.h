@@ -488,6 +488,26 @@ Result** group_aggregate_measures(GeneralizedColumn** columns, int** lows, int**
                                   GeneralizedColumn** meas_a, GeneralizedColumn** meas_b /* entries NULL for COL */,
                                   const int* ops, int nmeas /* 1..4 */, Status* ret_status);
 
+/* ---- HAVING, ORDER BY an aggregate and LIMIT over group results (not in the reference) ----
+ * group_top_k: the tail of a GROUP BY query (mq_topk64 in mq_device.h). `groups`
+ * is the array any group_aggregate* returned: nresults equally long Results, each INT or LONG
+ * (nkeys + 4 of them, or nkeys + 1 + 3 * nmeas from group_aggregate_measures). Tuple i passes
+ * when having_by is -1 or *low <= groups[having_by][i] < *high holds (either bound NULL:
+ * unbounded). The m = min(k, passing) first passing tuples of a stable sort by
+ * groups[order_by], ascending or descending, equal values in input (key) order both ways, are
+ * returned; order_by == -1 keeps the input order (HAVING and LIMIT alone; `descending` is
+ * ignored). Returns a new malloc'd array of nresults Result* with malloc'd payloads the caller
+ * frees, each of m tuples and of its input's data type; INT payloads keep an HBM shadow as
+ * every INT Result does. INT inputs are read through their shadow where they have one, LONG
+ * payloads are uploaded (they are small); ordering and gathers run on the device. The inputs
+ * are not consumed and not changed. k == 0 or no groups give empty Results and OK. ERROR and
+ * NULL (a "libmq:" line on stderr): no device, nresults < 1, an index out of range, a Result
+ * that is neither INT nor LONG, unequal lengths, 2^31 tuples or more, a device failure. */
+Result** group_top_k(Result** groups, int nresults, int order_by /* index into groups, or -1: keep key order */,
+                     bool descending, size_t k, int having_by /* index, or -1 */,
+                     const long* low, const long* high /* NULL: unbounded; low <= v < high */,
+                     Status* ret_status);
+
 /* ---- libmq residency control (not in the reference) ----
  * A device copy of host memory (a Column's rows, a Result payload, an index's
  * arrays) is reused by later operators only while a write guard proves the host
