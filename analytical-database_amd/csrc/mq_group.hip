@@ -722,51 +722,11 @@ constexpr uint32_t kNoSlot = ~0u;  // of a row with a component out of bounds: b
 // data a lane, 192 B with two and three key columns and 160 B with four.
 constexpr int by_tiles(int nkeys) { return nkeys == 2 ? 4 : nkeys == 3 ? 3 : 2; }
 
-struct ByArgs {
-    const int* keys[kMaxKeys];
-    uint32_t lo[kMaxKeys];
-    uint32_t rm1[kMaxKeys];     // range - 1: a range of 2^32 has no u32
-    uint32_t stride[kMaxKeys];  // mod 2^32: a stride of 2^32 (held as 0) only meets K_j - lo_j = 0
-};
-
 struct ByKeysOut {
     int32_t* keys[kMaxKeys];
 };
 
-// The code of one row's tuple; *in: every component lies within its own column's bounds. A
-// check of the sum would not do: (3, 12) under ranges (10, 10) sums to 42, inside the table.
-template <int NK>
-__device__ __forceinline__ uint32_t row_code(const ByArgs& a, const int (&k)[NK], bool* in) {
-    uint32_t c = 0;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < NK; j++) {
-        const uint32_t d = (uint32_t)k[j] - a.lo[j];  // a key below lo wraps past the range
-        ok = ok && d <= a.rm1[j];
-        c += d * a.stride[j];
-    }
-    *in = ok;
-    return c;
-}
-
-__device__ __forceinline__ int elem(const int4& q, int e) { return e == 0 ? q.x : e == 1 ? q.y : e == 2 ? q.z : q.w; }
-
-// The codes of a lane's four rows of one tile; bit e of *in: row e is within the bounds.
-template <int NK>
-__device__ __forceinline__ uint4 tile_codes(const ByArgs& a, const int4 (&k)[NK], uint32_t* in) {
-    uint32_t c[4], m = 0;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        int r[NK];
-#pragma unroll
-        for (int j = 0; j < NK; j++) r[j] = elem(k[j], e);
-        bool ok;
-        c[e] = row_code<NK>(a, r, &ok);
-        m |= ok ? 1u << e : 0u;
-    }
-    *in = m;
-    return make_uint4(c[0], c[1], c[2], c[3]);
-}
+// ByArgs, row_code and tile_codes, the tuple's code, are in mq_group_impl.h (mq_distinct.hip shares them).
 
 // k_group_dense over NK key columns: the slot is the tuple's code (range = the key space, at
 // most kDenseSlots), kNoSlot for a row out of bounds, so that a tile of 256 equal tuples is a
@@ -2103,6 +2063,44 @@ bool by_space(const int32_t* b, int nkeys, uint64_t* space) {
     return true;
 }
 
+// k_group_by_where_bounds and its fold over 1..4 key columns: *found = the matching rows' number and
+// every key column's min and max over them. Synchronises.
+int where_key_bounds(const DevState* s, const WhereArgs& w, bool vec, const int32_t* const* d_keys, int nkeys, uint64_t n,
+                     ByBounds* found, hipStream_t st, const char* who) {
+    ByArgs ka = {};
+    for (int j = 0; j < nkeys; j++) ka.keys[j] = d_keys[j];
+    uint32_t grid = 0;
+    ByBounds* part = nullptr;
+    auto launch = [&](auto nk) {
+        constexpr int NK = decltype(nk)::value;
+        const void* fn = vec ? reinterpret_cast<const void*>(&k_group_by_where_bounds<NK, true>)
+                             : reinterpret_cast<const void*>(&k_group_by_where_bounds<NK, false>);
+        uint64_t rpb;
+        geometry(s, n, fn, &grid, &rpb, (uint64_t)bw_tiles(NK) * kTileRows);
+        part = static_cast<ByBounds*>(pool_alloc(((size_t)grid + 1) * sizeof(ByBounds)));  // the blocks', then the result
+        if (!part) return set_err(MQ_ENOMEM, "%s: workspace allocation failed", who);
+        if (vec)
+            hipLaunchKernelGGL((k_group_by_where_bounds<NK, true>), dim3(grid), dim3(kTPB), 0, st, w, ka, n, rpb, part);
+        else
+            hipLaunchKernelGGL((k_group_by_where_bounds<NK, false>), dim3(grid), dim3(kTPB), 0, st, w, ka, n, rpb, part);
+        LAUNCHCHK("k_group_by_where_bounds");
+        return (int)MQ_OK;
+    };
+    int rc = nkeys == 1   ? launch(std::integral_constant<int, 1>{})
+             : nkeys == 2 ? launch(std::integral_constant<int, 2>{})
+             : nkeys == 3 ? launch(std::integral_constant<int, 3>{})
+                          : launch(std::integral_constant<int, 4>{});
+    if (!rc) {
+        hipLaunchKernelGGL(k_group_by_where_bounds_fold, dim3(1), dim3(kTPB), 0, st, part, grid, part + grid);
+        if (hipGetLastError() != hipSuccess) rc = set_err(MQ_EHIP, "launch of k_group_by_where_bounds_fold failed");
+    }
+    if (!rc && hipMemcpyAsync(found, part + grid, sizeof *found, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = set_err(MQ_EHIP, "%s: bounds download failed", who);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
+    pool_free(part);
+    return rc;
+}
+
 // The write of mq_group_write and mq_group_by_write: keys_out receives the key (one key
 // column), the slot (dense, nkeys > 1) or the sorted code (sort, nkeys > 1) of every group.
 int write_groups(mq_group* g, int32_t* keys_out, uint64_t* d_count_out, int64_t* d_sum_out, int32_t* d_min_out,
@@ -2151,6 +2149,34 @@ void group_launch_star_pack_pos(const StarArgs& a, uint32_t grid, const int32_t*
     else if (a.nterms == 2) launch(std::integral_constant<int, 2>{});
     else if (a.nterms == 3) launch(std::integral_constant<int, 3>{});
     else launch(std::integral_constant<int, 4>{});
+}
+
+int group_where_key_bounds(const DevState* s, const WhereArgs& w, bool vec, const int32_t* const* d_keys, int nkeys, uint64_t n,
+                           uint64_t* rows, int32_t* bounds, hipStream_t st, const char* who) {
+    ByBounds found = {};
+    const int rc = where_key_bounds(s, w, vec, d_keys, nkeys, n, &found, st, who);
+    if (rc) return rc;
+    *rows = found.count;
+    for (int j = 0; j < nkeys; j++) {
+        bounds[2 * j] = found.mn[j];
+        bounds[2 * j + 1] = found.mx[j];
+    }
+    return MQ_OK;
+}
+
+int group_launch_pack(const DevState* s, const ByArgs& a, int nkeys, uint64_t n, const int32_t* pos, uint64_t k, int32_t* packed,
+                      uint32_t** bad, uint32_t* nbad, hipStream_t st) {
+    bool vec = true;
+    for (int j = 0; j < nkeys; j++) vec = vec && aligned16(a.keys[j]);
+    auto launch = [&](auto nk) {
+        constexpr int NK = decltype(nk)::value;
+        if (pos) return launch_by_pack_pos<NK>(s, a, pos, k, n, packed, bad, nbad, st);
+        return vec ? launch_by_pack<NK, true>(s, a, n, packed, bad, nbad, st) : launch_by_pack<NK, false>(s, a, n, packed, bad, nbad, st);
+    };
+    return nkeys == 1   ? launch(std::integral_constant<int, 1>{})
+           : nkeys == 2 ? launch(std::integral_constant<int, 2>{})
+           : nkeys == 3 ? launch(std::integral_constant<int, 3>{})
+                        : launch(std::integral_constant<int, 4>{});
 }
 
 void group_launch_bad_total(const uint32_t* bad, uint32_t nbad, unsigned long long* total, hipStream_t st) {
@@ -2904,38 +2930,8 @@ int mq_group_by_where_plan(const int32_t* const* d_cols, const mq_range* h_range
     uint64_t rows = 0;
     bool rows_known = false;
     if (!h_key_bounds) {  // one more pass over the predicates and the key lines that hold a survivor
-        ByArgs ka = {};
-        for (int j = 0; j < nkeys; j++) ka.keys[j] = d_keys[j];
-        uint32_t grid = 0;
-        ByBounds* part = nullptr;
-        auto launch = [&](auto nk) {
-            constexpr int NK = decltype(nk)::value;
-            const bool vec = wvec && kvec;
-            const void* fn = vec ? reinterpret_cast<const void*>(&k_group_by_where_bounds<NK, true>)
-                                 : reinterpret_cast<const void*>(&k_group_by_where_bounds<NK, false>);
-            uint64_t rpb;
-            geometry(s, n, fn, &grid, &rpb, (uint64_t)bw_tiles(NK) * kTileRows);
-            part = static_cast<ByBounds*>(pool_alloc(((size_t)grid + 1) * sizeof(ByBounds)));  // the blocks', then the result
-            if (!part) return set_err(MQ_ENOMEM, "%s: workspace allocation failed", who);
-            if (vec)
-                hipLaunchKernelGGL((k_group_by_where_bounds<NK, true>), dim3(grid), dim3(kTPB), 0, st, w, ka, n, rpb, part);
-            else
-                hipLaunchKernelGGL((k_group_by_where_bounds<NK, false>), dim3(grid), dim3(kTPB), 0, st, w, ka, n, rpb, part);
-            LAUNCHCHK("k_group_by_where_bounds");
-            return (int)MQ_OK;
-        };
-        rc = nkeys == 2   ? launch(std::integral_constant<int, 2>{})
-             : nkeys == 3 ? launch(std::integral_constant<int, 3>{})
-                          : launch(std::integral_constant<int, 4>{});
         ByBounds found = {};
-        if (!rc) {
-            hipLaunchKernelGGL(k_group_by_where_bounds_fold, dim3(1), dim3(kTPB), 0, st, part, grid, part + grid);
-            if (hipGetLastError() != hipSuccess) rc = set_err(MQ_EHIP, "launch of k_group_by_where_bounds_fold failed");
-        }
-        if (!rc && hipMemcpyAsync(&found, part + grid, sizeof found, hipMemcpyDeviceToHost, st) != hipSuccess)
-            rc = set_err(MQ_EHIP, "%s: bounds download failed", who);
-        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_err(MQ_EHIP, "%s: stream failed", who);
-        pool_free(part);
+        rc = where_key_bounds(s, w, wvec && kvec, d_keys, nkeys, n, &found, st, who);  // synchronises
         if (rc) return fail(rc);
         if (found.count == 0) return no_groups();
         for (int j = 0; j < nkeys; j++) {

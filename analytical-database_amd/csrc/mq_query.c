@@ -1569,6 +1569,68 @@ Result** group_aggregate_by_where(GeneralizedColumn** columns, int** lows, int**
     return group_results(who, g, groups, nkeys, rc, ret_status);
 }
 
+/* COUNT(DISTINCT values) per tuple of `nkeys` key columns over the rows for which every range
+ * holds (no reference counterpart): nkeys + 1 Results, the key columns (INT),
+ * then the distinct counts (LONG). No bounds are passed (group_aggregate's reason): the plan
+ * finds the keys' and the values' ranges over the matching rows itself. */
+Result** group_count_distinct(GeneralizedColumn** columns, int** lows, int** highs, int ncols, GeneralizedColumn** keys,
+                              int nkeys, GeneralizedColumn* values, Status* ret_status) {
+    if (op_begin(ret_status)) return NULL;
+    const char* who = "group_count_distinct";
+    if (nkeys < 1 || nkeys > MQ_GROUP_MAX_KEYS) {
+        dml_fail(ret_status, who, "nkeys outside 1..4");
+        return NULL;
+    }
+    const int32_t* d_cols[MQ_WHERE_MAX_COLS];
+    const int32_t* dk[MQ_GROUP_MAX_KEYS];
+    const int32_t* dv = NULL;
+    mq_range ranges[MQ_WHERE_MAX_COLS];
+    size_t n = 0;
+    if (where_args_from(who, 0, 0, columns, lows, highs, ncols, values, d_cols, ranges, &dv, &n, ret_status)) return NULL;
+    const int a = by_keys(keys, nkeys, dk, &n, 1, ret_status);
+    if (a > 0) return NULL;
+    if (a) {
+        dml_fail(ret_status, who, a == -1 ? "every key must be a Column or an INT Result" : "the columns and keys differ in length");
+        return NULL;
+    }
+    mq_gdistinct* g = NULL;
+    uint64_t groups = 0;
+    int rc = mq_group_distinct_plan(d_cols, ranges, ncols, dk, nkeys, dv, n, NULL, NULL, MQ_GDISTINCT_AUTO, &g, &groups, NULL, g_stream);
+    void* buf = NULL;
+    /* one block: the counts (8 bytes an entry) first, then the keys */
+    if (!rc) rc = dev_alloc(&buf, groups ? (size_t)groups * (8 + 4 * (size_t)nkeys) : 16);
+    uint64_t* d_count = (uint64_t*)buf;
+    int32_t* d_keys[MQ_GROUP_MAX_KEYS];
+    for (int j = 0; j < nkeys; j++) d_keys[j] = (int32_t*)(d_count + groups) + (size_t)j * groups;
+    if (!rc) rc = mq_group_distinct_write(g, d_keys, d_count, g_stream);
+    mq_group_distinct_free(g); /* in g_stream's order, behind the write */
+    if (rc) {
+        mq_stream_sync(g_stream);
+        mq_pool_free(buf);
+        fail(ret_status, who, rc);
+        return NULL;
+    }
+    const int nres = nkeys + 1;
+    Result** out = (Result**)calloc((size_t)nres, sizeof(Result*));
+    for (int j = 0; j < nkeys; j++) out[j] = int_result_from_device(d_keys[j], (size_t)groups, ret_status);
+    out[nkeys] = long_result_from_device(d_count, (size_t)groups, ret_status);
+    mq_stream_sync(g_stream);
+    mq_pool_free(buf);
+    for (int i = 0; i < nres; i++)
+        if (!out[i]) {
+            for (int j = 0; j < nres; j++)
+                if (out[j]) {
+                    free(out[j]->payload);
+                    free(out[j]);
+                }
+            free(out);
+            ret_status->code = ERROR;
+            return NULL;
+        }
+    ret_status->code = OK;
+    return out;
+}
+
 /* group_aggregate_by over the fact rows for which every range holds and every joined dimension
  * has the row's foreign key, grouped by the tuple of the dimensions' attributes and the plain
  * fact columns among the terms (no reference counterpart). Every key map and

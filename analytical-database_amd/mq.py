@@ -31,6 +31,7 @@ MQ_AGG_KEY, MQ_AGG_COUNT, MQ_AGG_SUM, MQ_AGG_MIN, MQ_AGG_MAX = 0, 1, 2, 3, 4
 MQ_WHERE_MAX_COLS = 8
 MQ_SEMI_AUTO, MQ_SEMI_LDS, MQ_SEMI_GLOBAL = 0, 1, 2
 MQ_STAR_MAX_TERMS = 4
+MQ_GDISTINCT_AUTO, MQ_GDISTINCT_LDS, MQ_GDISTINCT_BITMAP, MQ_GDISTINCT_SORT = 0, 1, 2, 3
 MQ_GROUP_MAX_MEASURES = 4
 MQ_MEAS_COL, MQ_MEAS_ADD, MQ_MEAS_SUB, MQ_MEAS_MUL = 0, 1, 2, 3
 MQ_JOIN_STATE_WORDS = 3  # include/mq_device.h mq_join_state
@@ -68,6 +69,11 @@ class MqRange(C.Structure):  # include/mq_device.h mq_range
 
 class MqKeysetInfo(C.Structure):  # include/mq_device.h mq_keyset_info
     _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("distinct", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class MqGdistinctInfo(C.Structure):  # include/mq_device.h mq_gdistinct_info
+    _fields_ = [("path", C.c_int), ("space", C.c_uint64), ("span", C.c_uint64), ("bitmap_bytes", C.c_uint64),
+                ("rows", C.c_uint64), ("pairs", C.c_uint64)]
 
 
 class MqKeymapInfo(C.Structure):  # include/mq_device.h mq_keymap_info
@@ -283,6 +289,13 @@ _SIGS = {
                                       _vp]),
     "mq_group_measures_write": (_int, [_vp, C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "mq_group_measures_free": (_int, [_vp]),
+    "mq_group_distinct_lds_bytes": (_u64, []),
+    "mq_group_distinct_bitmap_bytes": (_u64, []),
+    "mq_group_distinct_auto_path": (_int, [C.POINTER(_i32), _int, C.POINTER(_i32), C.POINTER(_u64)]),
+    "mq_group_distinct_plan": (_int, [C.POINTER(_vp), C.POINTER(MqRange), _int, C.POINTER(_vp), _int, _vp, _u64, C.POINTER(_i32),
+                                      C.POINTER(_i32), _int, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(MqGdistinctInfo), _vp]),
+    "mq_group_distinct_write": (_int, [_vp, C.POINTER(_vp), _vp, _vp]),
+    "mq_group_distinct_free": (_int, [_vp]),
     "mq_reduce": (_int, [_vp, _u64, _vp, _vp, _sz, _vp]),
     "mq_add": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "mq_sub": (_int, [_vp, _vp, _u64, _vp, _vp]),
@@ -361,6 +374,10 @@ _SIGS = {
                                                   C.POINTER(C.POINTER(_int)), _int,
                                                   C.POINTER(C.POINTER(GeneralizedColumn)), _int,
                                                   C.POINTER(GeneralizedColumn), _PS]),
+    "group_count_distinct": (C.POINTER(_PR), [C.POINTER(C.POINTER(GeneralizedColumn)), C.POINTER(C.POINTER(_int)),
+                                              C.POINTER(C.POINTER(_int)), _int,
+                                              C.POINTER(C.POINTER(GeneralizedColumn)), _int,
+                                              C.POINTER(GeneralizedColumn), _PS]),
     "log_result": (None, [_PR]),
     "should_use_index": (C.c_bool, [C.POINTER(Column), _int, _int]),
     # load path (db_manager.h:254)

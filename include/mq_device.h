@@ -1013,6 +1013,72 @@ int mq_group_measures_write(mq_mgroup* g, int32_t* const* d_keys_out /* NULL or 
                             void* stream);
 int mq_group_measures_free(mq_mgroup* g);
 
+/* ---- COUNT(DISTINCT v) per group under a WHERE ----
+ *   SELECT k0, .., count(DISTINCT v) FROM t WHERE c0 IN [..) AND .. GROUP BY k0, ..
+ * With m[i] = every range holds for row i (mq_where_positions' meaning; ncols == 0: every row,
+ * d_cols and h_ranges may be NULL): one entry per distinct key tuple (nkeys in 1..MQ_GROUP_MAX_KEYS)
+ * that has a matching row, in ascending lexicographic signed order (mq_group_by_where_plan's order:
+ * the two operators' key outputs are identical), each with the number of different values of d_vals
+ * among the tuple's matching rows, as u64. Integer compares and bit sets only: the result is
+ * bitwise the same on every path, grid, alignment, predicate order and block finishing order.
+ * With P = prod(hi_j - lo_j + 1) of the key bounds, W = vhi - vlo + 1 of the value bounds and
+ * R = ceil(W / 32), a group's values are one row of R 32-bit words of a bitmap of P rows (the
+ * padding bits are never set and never counted):
+ * lds    (4 P R <= mq_group_distinct_lds_bytes()): one streaming pass in k_group_by_where_dense's
+ *        shape (the predicates, then the key and value lines that hold a survivor); a survivor
+ *        sets bit code * 32 R + (v - vlo) in a per-block LDS bitmap, which the block ORs into the
+ *        global bitmap at the end of its chunk.
+ * bitmap (4 P R <= mq_group_distinct_bitmap_bytes(), 512 MiB, the key set's cap): the same pass,
+ *        marking the zeroed global bitmap with mq_keyset_build's load-then-atomic-OR.
+ *        After either: one popcount per row, and the non-empty rows compacted in code order
+ *        (mq_select_positions with low = 1 over the counts, then mq_fetch).
+ * sort   (P <= 2^32, any W): mq_where_positions (skipped with ncols == 0), the packed codes of
+ *        mq_group_by_where_plan's sort path, the values gathered, mq_index_build by value and
+ *        then, stable, by code, so that the rows are in (code, value) order; a group's count is
+ *        the number of rows in its run whose code or value differs from the row before.
+ * MQ_GDISTINCT_AUTO takes the first path whose size rule holds; the rule is by size only, and
+ * nobody has measured where bitmap loses to sort. A forced path whose rule does not hold is
+ * MQ_EINVAL. Not measured on a device yet: DESIGN.md §3.22.
+ * Bounds (inclusive; h_key_bounds {lo_0, hi_0, ..}, h_val_bounds {vlo, vhi}) constrain MATCHING
+ * rows only: a key or value of a row that fails a predicate is never an error and never an
+ * address. Every key component and the value of a matching row is checked against its own
+ * bounds; a violation is MQ_EINVAL with everything released. NULL key bounds cost one more pass
+ * (k_group_by_where_bounds; one mq_reduce per key column with ncols == 0), NULL value bounds one
+ * mq_where_agg over the value column (one mq_reduce with ncols == 0).
+ * The plan SYNCHRONISES and finishes the whole computation: the handle owns only the groups'
+ * codes and counts, and no input needs to outlive the plan. The write is asynchronous and
+ * repeatable, skips NULL outputs and writes nothing at or past *h_groups entries. n == 0, a range
+ * that no int32 satisfies or no matching row give MQ_OK, zero groups and a handle to free (h_info:
+ * the forced path, or MQ_GDISTINCT_LDS, and zeros).
+ * MQ_EINVAL, with *out = NULL, *h_groups = 0 and nothing allocated: ncols outside 0..8, nkeys
+ * outside 1..4, n >= 2^31, a NULL or not 4-byte aligned pointer with n > 0, a NULL out or
+ * h_groups, a path outside the four, and of given bounds with n > 0 lo > hi, P > 2^32 or a
+ * forced path whose rule does not hold. */
+enum { MQ_GDISTINCT_AUTO = 0, MQ_GDISTINCT_LDS = 1, MQ_GDISTINCT_BITMAP = 2, MQ_GDISTINCT_SORT = 3 };
+typedef struct mq_gdistinct mq_gdistinct;
+typedef struct mq_gdistinct_info {
+    int      path;         /* the path taken */
+    uint64_t space;        /* P = prod(hi_j - lo_j + 1) of the key bounds used */
+    uint64_t span;         /* W = vhi - vlo + 1 of the value bounds used, up to 2^32 */
+    uint64_t bitmap_bytes; /* 4 * P * R, R = ceil(W / 32); 0 on the sort path */
+    uint64_t rows;         /* rows that passed the predicates */
+    uint64_t pairs;        /* distinct (tuple, value) pairs = the sum of the distinct counts */
+} mq_gdistinct_info;
+uint64_t mq_group_distinct_lds_bytes(void);     /* constants; need no device */
+uint64_t mq_group_distinct_bitmap_bytes(void);  /* 512 MiB, the key set's cap */
+/* needs no device: the path AUTO takes, or MQ_EINVAL (nkeys outside 1..4, a NULL pointer, a lo > hi,
+ * P > 2^32); *h_bitmap_bytes (may be NULL) = 4 * P * R, UINT64_MAX when P > 2^32 */
+int mq_group_distinct_auto_path(const int32_t* h_key_bounds, int nkeys, const int32_t* h_val_bounds,
+                                uint64_t* h_bitmap_bytes /* may be NULL; saturated */);
+int mq_group_distinct_plan(const int32_t* const* d_cols, const struct mq_range* h_ranges, int ncols /* 0..8 */,
+                           const int32_t* const* d_keys, int nkeys /* 1..4 */, const int32_t* d_vals, uint64_t n,
+                           const int32_t* h_key_bounds /* NULL or 2*nkeys */, const int32_t* h_val_bounds /* NULL or {lo,hi} */,
+                           int path, mq_gdistinct** out, uint64_t* h_groups, mq_gdistinct_info* h_info /* may be NULL */,
+                           void* stream);
+int mq_group_distinct_write(mq_gdistinct* g, int32_t* const* d_keys_out /* NULL, or nkeys ptrs, any NULL */,
+                            uint64_t* d_distinct_out /* may be NULL */, void* stream);
+int mq_group_distinct_free(mq_gdistinct* g);
+
 /* ---- S5 fetch_column: d_out[i] = d_col[d_pos[i]] ---- */
 int mq_fetch(const int32_t* d_col, const int32_t* d_pos, uint64_t k, int32_t* d_out, void* stream);
 /* the same from a row shard holding rows [row_base, row_base + rows) of the column:

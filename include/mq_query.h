@@ -488,6 +488,22 @@ Result** group_aggregate_measures(GeneralizedColumn** columns, int** lows, int**
                                   GeneralizedColumn** meas_a, GeneralizedColumn** meas_b /* entries NULL for COL */,
                                   const int* ops, int nmeas /* 1..4 */, Status* ret_status);
 
+/* ---- COUNT(DISTINCT v) per group under a WHERE (not in the reference) ----
+ * group_count_distinct: SELECT k0, .., count(DISTINCT v) FROM t WHERE c0 IN [..) AND .. GROUP BY
+ * k0, .. in one operator (mq_group_distinct_plan in mq_device.h). The arguments
+ * are group_aggregate_by_where's (Columns or INT Results, all equally long, any of them the same
+ * object); with ncols == 0 every row matches and `columns`, `lows` and `highs` may be NULL.
+ * Returns a malloc'd array of nkeys + 1 Results under group_aggregate's ownership and shadow
+ * rules: the key columns (INT, with HBM shadows), then the distinct counts (LONG), one tuple per
+ * distinct (k0, .., k_{nkeys-1}) that has a matching row, in ascending lexicographic order. No
+ * matching row gives nkeys + 1 empty Results and OK. No bounds are passed, for group_aggregate's
+ * reason: the plan finds the keys' and the values' ranges over the matching rows itself. Runs on
+ * the calling device; a column held as row shards drops them and is split again on next use.
+ * ERROR and NULL (a "libmq:" line on stderr): group_aggregate_by_where's cases, with ncols 0
+ * allowed. Not measured on a device yet. */
+Result** group_count_distinct(GeneralizedColumn** columns, int** lows, int** highs, int ncols /* 0..8 */,
+                              GeneralizedColumn** keys, int nkeys, GeneralizedColumn* values, Status* ret_status);
+
 /* ---- HAVING, ORDER BY an aggregate and LIMIT over group results (not in the reference) ----
  * group_top_k: the tail of a GROUP BY query (mq_topk64 in mq_device.h). `groups`
  * is the array any group_aggregate* returned: nresults equally long Results, each INT or LONG
