@@ -13,6 +13,30 @@
  *
  * The reference-facing drop-in (select_column, fetch_column, sum, ...) is in
  * mq_query.h; it is implemented in C on top of these entry points.
+ *
+ * Threads: any number of host threads may be inside these entry points at once, each
+ * on streams, buffers and workspaces of its own (tests/test_gpu_threads.py).
+ * Per thread: mq_last_error()'s message (the empty string until a call of the thread
+ *   fails); the delete plan and the insert plan (an apply step on a thread that made no
+ *   plan on that workspace is MQ_EINVAL); the state mq_shared_select_count leaves for
+ *   mq_shared_select_write; the pinned staging of the staged copies, the segmented
+ *   download and shared_select, freed by mq_thread_release(), which is a thread's last
+ *   libmq call.
+ * Shared, behind locks: the mq_pool_* allocator that every operator's scratch comes
+ *   from; the per-kernel occupancy cache; the arrival counters of the folded one-launch
+ *   forms (mq_select_agg, mq_select_sum, mq_select_fetch_agg, mq_reduce), one block per
+ *   device and stream, per thread as well for the per-thread default stream.
+ * May be shared between threads: a key set and a key map, once built (immutable, probed on
+ *   any stream); an mq_mgroup (mq_group_measures_write from several threads at once, into
+ *   different outputs: the write kernels only read the handle's buffers. Each write also
+ *   stores its stream in the handle, unsynchronised, and mq_group_measures_free frees in the
+ *   order of whichever stream was stored last: after concurrent writes, free only once
+ *   every write has completed, or queue one last write from the freeing thread on a live
+ *   stream first); any handle that one thread plans or builds and another, after
+ *   the first's work on it has completed, writes and frees. mq_group and mq_gdistinct
+ *   handles are written by one thread at a time.
+ * Not for concurrent use: mq_test_set_cu_limit and mq_release_all (no other thread
+ *   inside libmq), and the whole of mq_query.h, whose tables have no lock.
  */
 #ifndef MQ_DEVICE_H
 #define MQ_DEVICE_H

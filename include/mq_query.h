@@ -19,6 +19,10 @@
  * Device residency: a Column's rows are uploaded to HBM on first use and kept
  * while a write guard shows them unchanged; Results produced by libmq keep a
  * device shadow on the same terms (see "residency control" below).
+ * Threads: one caller at a time. The residency tables, the write guards and the
+ * shard configuration have no lock (the reference's server is one thread); the
+ * row-shard workers behind these entry points are libmq's own threads. Callers
+ * that want several threads inside libmq use mq_device.h (its "Threads" paragraph).
  */
 #ifndef MQ_QUERY_H
 #define MQ_QUERY_H
